@@ -10,7 +10,7 @@ build, probe, count back on the host), exactly HashJoiner::Run
 device before the timed region (the reference also times after generation,
 src/main.cpp:254 vs :100-102).
 
-N=1:  python bench.py [--steps K --warmup W]
+N=1:  python bench.py [--steps K --warmup W] [--full] [--dump-outputs DIR]
 N>1:  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
       Both relations are range-sharded (strong scaling: the 10M⋈200M
       workload is fixed); each rank's context (phj_ctx_create_rank) runs the
@@ -18,9 +18,16 @@ N>1:  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
       all-gathered and the count all-reduced over RCCL (csrc/phj_group.h).
 
 Rank 0 prints ONE JSON line. `roofline` is for the dominant kernel (longest
-per-step device time), from hipEvents on the stream the kernels run on;
-`cpu_baseline` times the oracle's restatement of the reference RadixCluster
-path (-p 1024, XXH3: its best published configuration) on this host.
+per-step device time), from hipEvents on the stream the kernels run on.
+
+A plain run sets up, warms up, times the steps and prints the line. --full
+adds what takes runs of its own: the rocprofv3 PMC traffic passes (child
+processes, before the GPU is touched here), the full-size correctness gates
+(`expected_matches`, the shifted-R check, `correct`) and `cpu_baseline`,
+which times the oracle's restatement of the reference RadixCluster path
+(-p 1024, XXH3: its best published configuration) on this host.
+--dump-outputs DIR writes what the last timed step returned to its caller
+(the match count) as DIR/matches.npy.
 """
 import argparse
 import json
@@ -45,10 +52,14 @@ def parse():
     ap.add_argument("--skew", type=float, default=None, help="Zipf skew of S (default: the config's)")
     ap.add_argument("--primary", type=int, default=NR)
     ap.add_argument("--secondary", type=int, default=NS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the PMC traffic passes, the full-size correctness gates and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result (the match count) as DIR/matches.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: the core share - 1 (cpu_threads)")
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 PMC passes")
     ap.add_argument("--all-timers", action="store_true",
                     help="time every phase in the timed loop (default: PHJ_LEAN_TIMERS, only S's pass 1 and the "
                          "LDS join; each event between two kernels delays the second by ~4 us)")
@@ -57,7 +68,10 @@ def parse():
                          "loop, PHJ_DEFER_TIMERS)")
     ap.add_argument("--exchange", action="store_true",
                     help="at one GPU, run the N>1 step (RCCL all-gather + all-reduce) on a world of one")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def config_params(phj, name):
@@ -245,7 +259,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # PMC passes first: child processes, before this process initialises the GPU
-    traffic = {} if (world > 1 or args.no_traffic) else pmc_traffic(args, args.verbose)
+    traffic = pmc_traffic(args, args.verbose) if (args.full and world == 1 and not args.no_traffic) else {}
     import torch
     import torch.distributed as dist
     import partitionedhashjoin_amd as phj
@@ -271,8 +285,8 @@ def main():
     ctx = rank_context(local_rank, rank, world, dist if exchange else None, exchange=args.exchange)
     generate_shards(ctx, nR, nS, alpha, GEN_SEED, rank, world)
     torch.cuda.synchronize()
-    # correctness gate at full size: every generated S key lies in [1, |R|]
-    local_inrange = ctx.count_in_range(1, 1, nR)
+    # correctness gate at full size (--full): every generated S key lies in [1, |R|]
+    local_inrange = ctx.count_in_range(1, 1, nR) if args.full else None
     ctx.prepare(params)   # workspace allocated outside the timed region
 
     radix = params.algo == phj.ALGO_RADIX
@@ -338,26 +352,41 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    inrange = allsum(local_inrange)
-    # a non-trivial full-size check after the timed region (the default inputs'
-    # answer is always |S|): R shifted to [1 + SHIFT, |R| + SHIFT] makes the
-    # hottest Zipf keys miss; the join must count exactly the S keys in range
-    # It runs the timed steps' own flags (DEFER|LEAN on one device: the count
-    # polled from pinned host memory, S's chunk state cleared by the previous
-    # join's last workgroup), three joins back to back, then the plain flags
-    shift = 3
-    generate_shards(ctx, nR, nS, alpha, GEN_SEED, rank, world, start=1 + shift)
-    shifted_expect = allsum(ctx.count_in_range(1, 1 + shift, nR))
-    shifted_runs, shifted_ms = [], []   # (host wall time per join: the misses' probe cost)
-    for p in [timed_params] * 3 + [params]:
-        t_join = time.perf_counter()
-        shifted_runs.append(ctx.join(p).matches)
-        shifted_ms.append(round((time.perf_counter() - t_join) * 1e3, 4))
-    if defer:
-        ctx.timers_report()   # (the check's deferred timers are not the bench's)
-    shifted_got = shifted_runs[0]
-    shifted_ok = all(m == shifted_expect for m in shifted_runs) and shifted_expect < inrange
-    generate_shards(ctx, nR, nS, alpha, GEN_SEED, rank, world)
+    if args.dump_outputs and rank == 0:
+        # what the timed path hands its caller: the last step's match count
+        # (exact in float64: at most |S| < 2^53)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "matches.npy"), np.array([int(matches)], dtype=np.float64))
+
+    checks = {}
+    if args.full:
+        inrange = allsum(local_inrange)
+        # a non-trivial full-size check after the timed region (the default inputs'
+        # answer is always |S|): R shifted to [1 + SHIFT, |R| + SHIFT] makes the
+        # hottest Zipf keys miss; the join must count exactly the S keys in range
+        # It runs the timed steps' own flags (DEFER|LEAN on one device: the count
+        # polled from pinned host memory, S's chunk state cleared by the previous
+        # join's last workgroup), three joins back to back, then the plain flags
+        shift = 3
+        generate_shards(ctx, nR, nS, alpha, GEN_SEED, rank, world, start=1 + shift)
+        shifted_expect = allsum(ctx.count_in_range(1, 1 + shift, nR))
+        shifted_runs, shifted_ms = [], []   # (host wall time per join: the misses' probe cost)
+        for p in [timed_params] * 3 + [params]:
+            t_join = time.perf_counter()
+            shifted_runs.append(ctx.join(p).matches)
+            shifted_ms.append(round((time.perf_counter() - t_join) * 1e3, 4))
+        if defer:
+            ctx.timers_report()   # (the check's deferred timers are not the bench's)
+        shifted_ok = all(m == shifted_expect for m in shifted_runs) and shifted_expect < inrange
+        generate_shards(ctx, nR, nS, alpha, GEN_SEED, rank, world)
+        checks = {
+            "expected_matches": inrange,
+            "shifted_check": {"build_start": 1 + shift, "expected": shifted_expect, "matches": shifted_runs[0],
+                              "runs": shifted_runs, "wall_ms": shifted_ms, "flags": int(timed_params.flags),
+                              "plain_flags": int(params.flags)},
+            "correct": int(matches) == inrange and shifted_ok,
+        }
 
     if rank == 0:
         per_step = {k: (v[0] / args.steps, v[1] / args.steps) for k, v in acc.items()}
@@ -390,11 +419,7 @@ def main():
                        "skew": alpha, "parallelism": f"range-shard x{world}"
                        + (" (exchange path)" if exchange and world == 1 else "")},
             "matches": int(matches),
-            "expected_matches": inrange,
-            "shifted_check": {"build_start": 1 + shift, "expected": shifted_expect, "matches": shifted_got,
-                              "runs": shifted_runs, "wall_ms": shifted_ms, "flags": int(timed_params.flags),
-                              "plain_flags": int(params.flags)},
-            "correct": int(matches) == inrange and shifted_ok,
+            **checks,   # --full: expected_matches, shifted_check, correct
             "exchange_ms": exch / args.steps if exchange else None,
             "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": achieved,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -405,7 +430,7 @@ def main():
             "kernels_ms": {k: round(v[0], 4) for k, v in sorted(per_step.items())},
             "kernels_traffic_bytes": {k: int(v) for k, v in sorted(traffic.items())} or None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = args.cpu_threads or cpu_threads(host_cpu())
             cb = cpu_baseline(ctx, nR, nS, threads, args.verbose)
             out["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample")}

@@ -36,18 +36,18 @@ for step in "$@"; do
       timeout -k 10 900 python -u -m pytest $(echo ${step#tests=} | tr ',' ' ') -m gpu -x -q --timeout 300 --timeout-method thread > ${O}_pytest.log 2>&1 || { echo "pytest failed"; tail -40 ${O}_pytest.log; exit 1; }
       tail -1 ${O}_pytest.log ;;
     bench)
-      timeout -k 10 500 python bench.py --verbose > ${O}_bench_c2.json 2> ${O}_bench_c2.err || { echo "bench failed"; tail -5 ${O}_bench_c2.err; exit 2; }
+      timeout -k 10 500 python bench.py --full --verbose > ${O}_bench_c2.json 2> ${O}_bench_c2.err || { echo "bench failed"; tail -5 ${O}_bench_c2.err; exit 2; }
       cut -c1-1500 ${O}_bench_c2.json ;;
     quick)
-      timeout -k 10 200 python bench.py --no-cpu-baseline --no-traffic --verbose > ${O}_quick.json 2> ${O}_quick.err || { echo "bench failed"; tail -5 ${O}_quick.err; exit 2; }
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-traffic --verbose > ${O}_quick.json 2> ${O}_quick.err || { echo "bench failed"; tail -5 ${O}_quick.err; exit 2; }
       cut -c1-1200 ${O}_quick.json ;;
     c4c5)
       for c in c4 c5; do
-        timeout -k 10 400 python bench.py --config $c --no-cpu-baseline > ${O}_bench_$c.json 2> ${O}_bench_$c.err || { echo "bench $c failed"; tail -5 ${O}_bench_$c.err; exit 3; }
+        timeout -k 10 400 python bench.py --full --config $c --no-cpu-baseline > ${O}_bench_$c.json 2> ${O}_bench_$c.err || { echo "bench $c failed"; tail -5 ${O}_bench_$c.err; exit 3; }
         python -c "import json; d=json.load(open('${O}_bench_$c.json')); print('$c', round(d['ms_per_step'],3), d['correct'], d['kernels_ms'], d['roofline'])"
       done ;;
     exchange)
-      timeout -k 10 200 python bench.py --exchange --no-cpu-baseline --no-traffic > ${O}_bench_exchange.json 2> ${O}_bench_exchange.err || { echo "exchange failed"; tail -5 ${O}_bench_exchange.err; exit 4; }
+      timeout -k 10 200 python bench.py --full --exchange --no-cpu-baseline --no-traffic > ${O}_bench_exchange.json 2> ${O}_bench_exchange.err || { echo "exchange failed"; tail -5 ${O}_bench_exchange.err; exit 4; }
       cut -c1-600 ${O}_bench_exchange.json ;;
     stats)
       prof stats_c2 --steps 20 --warmup 3 --no-cpu-baseline --no-traffic || exit 5
