@@ -281,10 +281,46 @@ typedef struct phj_joined {
  * partition order for the radix join). The radix form needs one build
  * segment. Synchronous; r->matches = number of rows. */
 int phj_join_materialize(phj_ctx *ctx, const phj_join_params *p, phj_join_result *r);
-/* The rows of the last phj_join_materialize: device pointer (ctx-owned, valid
- * until the next materialised join) and count. */
+/* ---- inner join with duplicate build keys ----
+ * Replaces nothing in the reference, whose Get() stops at the first hit:
+ * phj_join and phj_join_materialize answer the semi-join question (one count /
+ * one row per probe tuple that has a match). These two compute R ⋈ S itself.
+ *
+ * phj_join_inner_count: r->matches = |R ⋈ S|, the number of (build tuple,
+ * probe tuple) pairs with equal ids, exact in 64 bits; no rows. No size limit
+ * beyond those of phj_join (each side below 2^32 tuples). The rows of an
+ * earlier materialised join stay as they are.
+ *
+ * phj_join_inner: the same join, materialised: one phj_joined row {id, that
+ * build tuple's payload, the probe tuple's payload} per pair, into the
+ * ctx-owned row buffer that phj_joined_rows / phj_joined_download serve;
+ * r->matches = number of rows. A later phj_join_materialize replaces the rows,
+ * and the reverse holds too.
+ *  - PHJ_ALGO_RADIX and PHJ_ALGO_NO_PARTITIONING are both supported; the radix
+ *    form has phj_join_materialize's precondition (the fused LDS join: one
+ *    build segment, partitions of ~170 build tuples on average, which the
+ *    default sub-partitioning provides).
+ *  - Single-device contexts only: a group or rank context returns
+ *    PHJ_ERR_STATE ("single-device contexts only").
+ *  - Rows are grouped by probe tuple: all rows of one probe tuple are
+ *    contiguous, and the groups come in the probe side's storage order (input
+ *    order for NoPartitioning, partition order for the radix join). The order
+ *    of the build matches inside a group is unspecified.
+ *  - Rows are addressed with 32 bits. With 2^32 pairs or more phj_join_inner
+ *    returns PHJ_ERR_RANGE before any row is written or the row buffer is
+ *    grown; r->matches still holds the 64-bit pair count, and phj_joined_rows
+ *    then reports 0 rows.
+ *  - An empty build or probe side gives 0 pairs and no error.
+ *  - Two passes over the same join (count, then emit at scanned offsets):
+ *    timers `inner.count` and `inner.emit` beside the partition / build timers;
+ *    algorithmic_bytes counts what both passes must move (DESIGN.md §Inner join).
+ * Synchronous. */
+int phj_join_inner_count(phj_ctx *ctx, const phj_join_params *p, phj_join_result *r);
+int phj_join_inner(phj_ctx *ctx, const phj_join_params *p, phj_join_result *r);
+/* The rows of the last phj_join_materialize / phj_join_inner: device pointer
+ * (ctx-owned, valid until the next materialised join) and count. */
 const phj_joined *phj_joined_rows(phj_ctx *ctx, uint64_t *n);
-/* Copy the first n rows of the last phj_join_materialize to host memory. */
+/* Copy the first n rows of the last phj_join_materialize / phj_join_inner to host memory. */
 int phj_joined_download(phj_ctx *ctx, phj_joined *host, uint64_t n);
 
 /* ---- building blocks (multi-GPU: range-sharded relations, RCCL exchange) ---- */

@@ -257,6 +257,21 @@ class Context:
         self._check(self._L.phj_join_materialize(self._h, C.byref(params), C.byref(r)))
         return r
 
+    def join_inner_count(self, params: JoinParams) -> JoinResult:
+        """phj_join_inner_count: r.matches = |R join S|, the number of (build
+        tuple, probe tuple) pairs with equal ids (64-bit exact); no rows."""
+        r = JoinResult()
+        self._check(self._L.phj_join_inner_count(self._h, C.byref(params), C.byref(r)))
+        return r
+
+    def join_inner(self, params: JoinParams) -> JoinResult:
+        """phj_join_inner: the inner join's rows, one per (build tuple, probe
+        tuple) pair, grouped by probe tuple; r.matches rows. Read them with
+        joined(). Raises PhjError (PHJ_ERR_RANGE) at 2^32 pairs or more."""
+        r = JoinResult()
+        self._check(self._L.phj_join_inner(self._h, C.byref(params), C.byref(r)))
+        return r
+
     def joined(self, n: int | None = None) -> np.ndarray:
         """Rows of the last materialised join as an (n, 3) int64 array
         {id, payloadA (build), payloadB (probe)}."""

@@ -40,6 +40,7 @@ EXPORTED = [
     "phj_ctx_create_ex", "phj_ctx_create_device", "phj_comm_unique_id", "phj_ctx_create_rank",
     "phj_ctx_info", "phj_shard_range", "phj_probe_pass1", "phj_debug_poison_chunk_table", "phj_debug_poison_alloc", "phj_debug_fail_member", "phj_debug_exchange_block", "phj_exchange_geometry",
     "phj_exchange_layout", "phj_count_contribution", "phj_count_verdict", "phj_join_path",
+    "phj_join_inner_count", "phj_join_inner",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
@@ -145,6 +146,8 @@ def load():
         "phj_join_partitioned_async": (i, [P, C.POINTER(JoinParams), i, C.POINTER(Partitioned), P]),
         "phj_prepare": (i, [P, C.POINTER(JoinParams)]),
         "phj_join_materialize": (i, [P, C.POINTER(JoinParams), C.POINTER(JoinResult)]),
+        "phj_join_inner_count": (i, [P, C.POINTER(JoinParams), C.POINTER(JoinResult)]),
+        "phj_join_inner": (i, [P, C.POINTER(JoinParams), C.POINTER(JoinResult)]),
         "phj_joined_rows": (P, [P, C.POINTER(u64)]),
         "phj_joined_download": (i, [P, P, u64]),
     }

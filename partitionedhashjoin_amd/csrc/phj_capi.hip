@@ -32,6 +32,7 @@
 #include "../../include/phj.h"
 #include "phj_cluster.h"
 #include "phj_join.h"
+#include "phj_inner.h"
 #include "phj_mat.h"
 #include "phj_partition.h"
 #include "phj_table.h"
@@ -1812,25 +1813,21 @@ int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     return fill_timers(c, r);
 }
 
-// marks != nullptr: the probe also writes, per probe tuple, its match's payload
-// slot (phj_join_materialize)
-int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32_t* marks = nullptr) {
+// The NoPartitioning bucket table (np_tab, np_pays) over the build side: R
+// radix-partitioned into the table's regions, one workgroup per region, then
+// the overflow list. g: the table's geometry. slots32: every slot index
+// b * 7 + s must stay below kNoMatch (the materialising probes store it in 32
+// bits). *e0 is recorded before the first kernel. Under phj_prepare (c->dry)
+// only the workspace is sized.
+int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipEvent_t* e0) {
     SideState& R = c->side[PHJ_SIDE_BUILD];
-    SideState& S = c->side[PHJ_SIDE_PROBE];
-    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
-        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
-    if (R.n == 0)  // LinearProbing.hpp:295-299
-        return set_err(c, PHJ_ERR_INVALID,
-                       "LinearProbingHashTable::LinearProbingHashTable: numberOfObjects must be greater than zero.");
-    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
-    if (!marks && R.n < (1ull << 30)) return join_nopart_ct(c, p, r);
     const double ratio = p->table_ratio > 0 ? p->table_ratio : kNPDefaultRatio;
     if (ratio < 1.0) return set_err(c, PHJ_ERR_INVALID, "table_ratio must be >= 1");
     const double nbd = std::ceil(static_cast<double>(R.n) * ratio / kNPSlots);
     if (nbd >= 4294967295.0) return set_err(c, PHJ_ERR_RANGE, "table too large");
     const uint32_t nb0 = std::max<uint32_t>(1, static_cast<uint32_t>(nbd));
     // region build: 2^rbits regions of <= kNPRegionBuckets buckets (LDS-sized)
-    NPHome g{nb0, nb0, 0, 0};
+    g = NPHome{nb0, nb0, 0, 0};
     g.rbits = std::min<uint32_t>(22, std::max<uint32_t>(1, ceil_log2((nb0 + kNPRegionBuckets - 1) / kNPRegionBuckets)));
     g.nbr = (nb0 + (1u << g.rbits) - 1) >> g.rbits;
     const uint64_t nbw = static_cast<uint64_t>(g.nbr) << g.rbits;
@@ -1839,7 +1836,7 @@ int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32
     const uint32_t nb = g.nb;
     // the materialising probe stores a match as the uint32 slot b * 7 + s, and
     // kNoMatch (0xffffffff) must stay out of that range
-    if (marks && static_cast<uint64_t>(nb) * kNPSlots >= kNoMatch)
+    if (slots32 && static_cast<uint64_t>(nb) * kNPSlots >= kNoMatch)
         return set_err(c, PHJ_ERR_RANGE, "materialised NoPartitioning join: table above 2^32 - 1 slots");
     PHJ_TRY(ensure(c, c->np_tab, static_cast<size_t>(nb) * sizeof(NPBucket)));
     PHJ_TRY(ensure(c, c->np_pays, static_cast<size_t>(nb) * kNPSlots * 8));
@@ -1858,9 +1855,8 @@ int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32
         PHJ_TRY(make_plan(c, &pp, rp));
         if (c->dry) return partition_side(c, PHJ_SIDE_BUILD, rp);
     }
-    hipEvent_t e0, e1, e2;
     const uint32_t nR = static_cast<uint32_t>(R.n);
-    PHJ_TRY(mark(c, &e0));
+    PHJ_TRY(mark(c, e0));
     {
         // the partition is part of the build (its R.* timers show it)
         PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, rp));
@@ -1885,6 +1881,26 @@ int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32
         PHJ_LAUNCHED(c, "k_np_build_overflow");
         PHJ_TRY(timer_end(c));
     }
+    return PHJ_OK;
+}
+
+// marks != nullptr: the probe also writes, per probe tuple, its match's payload
+// slot (phj_join_materialize)
+int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32_t* marks = nullptr) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
+        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
+    if (R.n == 0)  // LinearProbing.hpp:295-299
+        return set_err(c, PHJ_ERR_INVALID,
+                       "LinearProbingHashTable::LinearProbingHashTable: numberOfObjects must be greater than zero.");
+    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (!marks && R.n < (1ull << 30)) return join_nopart_ct(c, p, r);
+    NPHome g{};
+    hipEvent_t e0 = nullptr, e1, e2;
+    PHJ_TRY(np_build(c, p, marks != nullptr, g, &e0));
+    if (c->dry) return PHJ_OK;
+    const uint32_t nb = g.nb;
     PHJ_TRY(mark(c, &e1));
     PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
     if (S.n > 0) {
@@ -2026,6 +2042,212 @@ int join_radix_mark(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     r->num_partitions = requested;
     r->algorithmic_bytes = partition_bytes(pl, R.n) + partition_bytes(pl, S.n) + R.n * 8 + nS * 12 + m * 24;
     return fill_timers(c, r);
+}
+
+// ---- the inner join (phj_inner.h): count, offsets, emit ----
+
+constexpr uint64_t kInnerRowLimit = 1ull << 32;   // rows are addressed with 32 bits (scan_u32)
+
+int inner_range_error(phj_ctx* c, uint64_t pairs) {
+    return set_err(c, PHJ_ERR_RANGE, "phj_join_inner: " + std::to_string(pairs) +
+                                         " pairs, rows are addressed with 32 bits (limit 2^32 - 1)");
+}
+
+// Pass 2 of the inner join: pairs[0, nS) (mat_mark) -> each probe tuple's
+// first row, in place. Launched inside the caller's "inner.emit" timer.
+int inner_offsets(phj_ctx* c, uint64_t nS) {
+    const uint32_t nblk = static_cast<uint32_t>((nS + kMatBlock - 1) / kMatBlock);
+    auto* cnt = static_cast<uint32_t*>(c->mat_cnt.p);
+    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
+    PHJ_HIP(c, hipMemsetAsync(cnt, 0, (static_cast<size_t>(nblk) + 1) * 4, c->ks));
+    hipLaunchKernelGGL(k_inner_blocksum, dim3(nblk), dim3(kBlock), 0, c->ks, pairs, nS, cnt);
+    PHJ_LAUNCHED(c, "k_inner_blocksum");
+    PHJ_TRY(scan_u32(c, cnt, nblk + 1, 1, nblk + 1));
+    hipLaunchKernelGGL(k_inner_prefix, dim3(nblk), dim3(kBlock), 0, c->ks, pairs, nS, cnt);
+    PHJ_LAUNCHED(c, "k_inner_prefix");
+    return PHJ_OK;
+}
+
+// Bytes the two passes must move, beyond partitioning / the table build
+// (DESIGN.md §Inner join): the count pass reads the probe keys and the build
+// keys and writes pairs[]; the offsets read pairs[] twice and write it once;
+// the emit pass reads the build keys, the probe tuples and pairs[] again and,
+// per row, gathers a build payload and writes 24 B.
+uint64_t inner_count_bytes(uint64_t nR, uint64_t nS) { return nR * 8 + nS * (8 + 4); }
+uint64_t inner_emit_bytes(uint64_t nR, uint64_t nS, uint64_t rows) {
+    return nS * 12 + nR * 8 + nS * (16 + 4) + rows * (8 + 24);
+}
+
+int join_nopart_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
+        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
+    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (S.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    NPHome g{};
+    hipEvent_t e0 = nullptr, e1, e2;
+    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));
+    PHJ_TRY(np_build(c, p, true, g, &e0));
+    PHJ_TRY(mark(c, &e1));
+    PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
+    const auto* S_rel = reinterpret_cast<const longlong2*>(S.rel);
+    const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
+    const auto* pays = static_cast<const int64_t*>(c->np_pays.p);
+    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
+    auto* cnt = static_cast<unsigned long long*>(c->count.p);
+    const uint64_t table_bytes = static_cast<uint64_t>(g.nb) * 64;
+    PHJ_TRY(timer_begin(c, "inner.count", inner_count_bytes(0, S.n) + table_bytes));
+    if (p->hash == PHJ_HASH_MURMUR3)
+        hipLaunchKernelGGL((k_np_inner<kMurmur3, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
+                           g, p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
+    else
+        hipLaunchKernelGGL((k_np_inner<kXXH3, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
+                           p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
+    PHJ_LAUNCHED(c, "k_np_inner");
+    PHJ_TRY(timer_end(c));
+    PHJ_TRY(mark(c, &e2));
+    uint64_t m = 0;
+    PHJ_TRY(get_count(c, &m));
+    r->matches = m;
+    r->algorithmic_bytes = R.n * 32 + table_bytes + inner_count_bytes(0, S.n) + table_bytes;
+    if (emit) {
+        // nothing is written and the row buffer is not grown above the limit
+        if (m >= kInnerRowLimit) return inner_range_error(c, m);
+        const uint32_t nblk = static_cast<uint32_t>((S.n + kMatBlock - 1) / kMatBlock);
+        PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
+        PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, m) * sizeof(JoinedRow)));
+        auto* rows = static_cast<JoinedRow*>(c->mat_rows.p);
+        PHJ_TRY(timer_begin(c, "inner.emit", inner_emit_bytes(0, S.n, m) + table_bytes));
+        PHJ_TRY(inner_offsets(c, S.n));
+        if (p->hash == PHJ_HASH_MURMUR3)
+            hipLaunchKernelGGL((k_np_inner<kMurmur3, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
+                               g, p->hash_seed, pairs, cnt, rows, static_cast<uint32_t>(m));
+        else
+            hipLaunchKernelGGL((k_np_inner<kXXH3, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
+                               g, p->hash_seed, pairs, cnt, rows, static_cast<uint32_t>(m));
+        PHJ_LAUNCHED(c, "k_np_inner");
+        PHJ_TRY(timer_end(c));
+        PHJ_TRY(mark(c, &e2));
+        PHJ_HIP(c, hipStreamSynchronize(c->ks));
+        r->algorithmic_bytes += inner_emit_bytes(0, S.n, m) + table_bytes;
+    }
+    r->partition_ms = 0;
+    r->build_ms = elapsed(c, e0, e1);
+    r->probe_ms = elapsed(c, e1, e2);
+    r->total_ms = elapsed(c, e0, e2);
+    r->num_partitions = 0;
+    return fill_timers(c, r);
+}
+
+// The radix form: both sides fully partitioned (SoA), then the per-partition
+// LDS join twice (join_radix_mark's precondition: the fused LDS join).
+int join_radix_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit) {
+    Plan pl;
+    PHJ_TRY(make_plan(c, p, pl));
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    const uint32_t requested = pl.Ppad;
+    refine_plan(c, pl, R.n);
+    const uint32_t P = pl.Ppad;
+    if (!c->tune.fused || (R.n + P - 1) / P * 3 > static_cast<uint64_t>(kFusedTcap) * 2)
+        return set_err(c, PHJ_ERR_INVALID, "radix inner join needs the fused LDS join (PHJ_FUSED, PHJ_SUBPART)");
+    if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    hipEvent_t t0, t1, p1;
+    PHJ_TRY(mark(c, &t0));
+    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl));
+    PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, pl));
+    PHJ_TRY(mark(c, &t1));
+    const uint64_t nS = S.view.n;
+    const size_t nslots = nS / kFusedChunk + P + 1;
+    PHJ_TRY(ensure(c, c->fitems, nslots * sizeof(FusedItem)));
+    PHJ_TRY(ensure(c, c->count, 32));
+    PHJ_TRY(ensure(c, c->mat_mark, nS * 4));
+    PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
+    PHJ_TRY(timer_begin(c, "inner.count", inner_count_bytes(R.n, nS)));
+    hipLaunchKernelGGL(k_fused_items, dim3((P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, S.view.bounds, P,
+                       static_cast<FusedItem*>(c->fitems.p));
+    PHJ_LAUNCHED(c, "k_fused_items");
+    FusedArgs fa{};
+    fa.L.nseg = 1;
+    fa.L.P = P;
+    fa.L.seg[0].keys = R.view.keys;
+    fa.L.seg[0].pays = R.view.payloads;
+    fa.L.seg[0].bounds = R.view.bounds;
+    fa.skeys = S.view.keys;
+    fa.sbounds = S.view.bounds;
+    fa.items = static_cast<const FusedItem*>(c->fitems.p);
+    fa.nitems = static_cast<uint32_t>(nslots - 1);
+    fa.count = static_cast<unsigned long long*>(c->count.p);
+    fa.seed = pl.seed;
+    const uint32_t grid = static_cast<uint32_t>(
+        std::max<size_t>(1, std::min<size_t>((nslots + kWaves - 1) / kWaves, static_cast<size_t>(4) * c->num_cus)));
+    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
+    if (pl.hk == kMurmur3)
+        hipLaunchKernelGGL((k_inner_fused<kMurmur3, false>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
+                           S.view.payloads, static_cast<JoinedRow*>(nullptr), 0u);
+    else
+        hipLaunchKernelGGL((k_inner_fused<kXXH3, false>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
+                           S.view.payloads, static_cast<JoinedRow*>(nullptr), 0u);
+    PHJ_LAUNCHED(c, "k_inner_fused");
+    PHJ_TRY(timer_end(c));
+    PHJ_TRY(mark(c, &p1));
+    uint64_t m = 0;
+    PHJ_TRY(get_count(c, &m));
+    r->matches = m;
+    r->num_partitions = requested;
+    r->algorithmic_bytes = partition_bytes(pl, R.n) + partition_bytes(pl, S.n) + inner_count_bytes(R.n, nS);
+    if (emit) {
+        // nothing is written and the row buffer is not grown above the limit
+        if (m >= kInnerRowLimit) return inner_range_error(c, m);
+        const uint32_t nblk = static_cast<uint32_t>((nS + kMatBlock - 1) / kMatBlock);
+        PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
+        PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, m) * sizeof(JoinedRow)));
+        auto* rows = static_cast<JoinedRow*>(c->mat_rows.p);
+        PHJ_TRY(timer_begin(c, "inner.emit", inner_emit_bytes(R.n, nS, m)));
+        PHJ_TRY(inner_offsets(c, nS));
+        if (pl.hk == kMurmur3)
+            hipLaunchKernelGGL((k_inner_fused<kMurmur3, true>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
+                               S.view.payloads, rows, static_cast<uint32_t>(m));
+        else
+            hipLaunchKernelGGL((k_inner_fused<kXXH3, true>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
+                               S.view.payloads, rows, static_cast<uint32_t>(m));
+        PHJ_LAUNCHED(c, "k_inner_fused");
+        PHJ_TRY(timer_end(c));
+        PHJ_TRY(mark(c, &p1));
+        PHJ_HIP(c, hipStreamSynchronize(c->ks));
+        r->algorithmic_bytes += inner_emit_bytes(R.n, nS, m);
+    }
+    r->partition_ms = elapsed(c, t0, t1);
+    r->probe_ms = elapsed(c, t1, p1);
+    r->total_ms = elapsed(c, t0, p1);
+    return fill_timers(c, r);
+}
+
+// phj_join_inner_count (emit = false) / phj_join_inner.
+int join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit, const char* what) {
+    if (!c || !r) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    (void)hipGetLastError();
+    if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    std::memset(r, 0, sizeof(*r));
+    c->defer_timers = false;
+    c->lean_timers = false;
+    c->timer_skipped = false;
+    c->count_pinned = false;
+    reset_timers(c);
+    if (emit) c->mat_n = 0;
+    if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
+        return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    // an empty side joins to nothing (no table to build, no pass to run)
+    if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0) return PHJ_OK;
+    if (p->algo == PHJ_ALGO_NO_PARTITIONING) PHJ_TRY(join_nopart_inner(c, p, r, emit));
+    else PHJ_TRY(join_radix_inner(c, p, r, emit));
+    if (emit) c->mat_n = r->matches;
+    return PHJ_OK;
 }
 
 int ctx_create_device(int device, phj_ctx** out) {
@@ -2814,6 +3036,14 @@ int phj_join_materialize(phj_ctx* c, const phj_join_params* p, phj_join_result* 
     }
     c->mat_n = r->matches;
     return PHJ_OK;
+}
+
+int phj_join_inner_count(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
+    return join_inner(c, p, r, false, "phj_join_inner_count");
+}
+
+int phj_join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
+    return join_inner(c, p, r, true, "phj_join_inner");
 }
 
 const phj_joined* phj_joined_rows(phj_ctx* c, uint64_t* n) {

@@ -11,8 +11,10 @@
 // drives the timer with the device-measured phase times and, like the
 // reference, returns an empty Table<JoinedTuple> (counts only) unless
 // GpuConfiguration::Materialize asks for the rows (phj_join_materialize:
-// one JoinedTuple per matching probe tuple, copied back); the matched
-// count is logged ("Joined N tuples", RadixCluster/HashJoin.hpp:320-321),
+// one JoinedTuple per matching probe tuple, copied back) or
+// GpuConfiguration::MaterializeAll for the inner join's (phj_join_inner: one
+// per pair of a build and a probe tuple with equal ids); the matched
+// count (MaterializeAll: the pair count) is logged ("Joined N tuples", RadixCluster/HashJoin.hpp:320-321),
 // added to the results as `matches`, and kept in GetNumberOfJoinedTuples().
 // C ABI errors surface as std::runtime_error / std::invalid_argument, which the
 // CLI catches and turns into exit(1) (src/main.cpp:277-281).
@@ -79,16 +81,18 @@ inline std::chrono::nanoseconds ms_to_ns(double ms) {
     return std::chrono::nanoseconds(static_cast<int64_t>(std::llround(ms * 1e6)));
 }
 
-// phj_join or, with rows requested, phj_join_materialize + the rows copied
-// into the returned table
+// phj_join or, with rows requested, phj_join_materialize (one row per matching
+// probe tuple) / phj_join_inner (all: one row per pair) + the rows copied into
+// the returned table
 inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, const phj_join_params& p,
-                                                                phj_join_result& r, bool materialize) {
-    if (!materialize) {
+                                                                phj_join_result& r, bool materialize,
+                                                                bool all = false) {
+    if (!materialize && !all) {
         dev.Check(phj_join(dev.Get(), &p, &r));
         return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());
     }
     static_assert(sizeof(Common::JoinedTuple) == sizeof(phj_joined), "JoinedTuple layout");
-    dev.Check(phj_join_materialize(dev.Get(), &p, &r));
+    dev.Check(all ? phj_join_inner(dev.Get(), &p, &r) : phj_join_materialize(dev.Get(), &p, &r));
     auto out = std::make_shared<Common::Table<Common::JoinedTuple>>(r.matches, Common::generate_uuid());
     dev.Check(phj_joined_download(dev.Get(), reinterpret_cast<phj_joined*>(out->Data()), r.matches));
     return out;
@@ -153,7 +157,7 @@ class HashJoiner {
         // workspace allocation stays outside the timed phases, as the reference's
         // partitioned-table allocation does (RadixCluster/HashJoin.hpp:195-198)
         m_device->Check(phj_prepare(m_device->Get(), &p));
-        auto joined = internal::join(*m_device, p, r, m_gpu.Materialize);
+        auto joined = internal::join(*m_device, p, r, m_gpu.Materialize, m_gpu.MaterializeAll);
         // partition: wall of both partition pipelines; build / probe: device phases
         timer->SetPartitionPhaseDuration(internal::ms_to_ns(r.partition_ms));
         timer->SetBuildPhaseDuration(internal::ms_to_ns(r.build_ms));
@@ -220,7 +224,7 @@ class HashJoiner {
         // workspace allocation stays outside the timed phases, as the reference's
         // partitioned-table allocation does (RadixCluster/HashJoin.hpp:195-198)
         m_device->Check(phj_prepare(m_device->Get(), &p));
-        auto joined = internal::join(*m_device, p, r, m_gpu.Materialize);
+        auto joined = internal::join(*m_device, p, r, m_gpu.Materialize, m_gpu.MaterializeAll);
         timer->SetBuildPhaseDuration(internal::ms_to_ns(r.build_ms));
         // the reference's probe figure runs from the build start (Results.hpp:202)
         timer->SetProbePhaseDuration(internal::ms_to_ns(r.build_ms + r.probe_ms));

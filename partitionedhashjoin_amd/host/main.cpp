@@ -63,14 +63,15 @@ const char* kHelp =
     "  --hash-seed arg                     Hasher seed (default: random).\n"
     "  --generate arg (=host)              host | device.\n"
     "  --table-ratio arg                   No-partitioning table slots per build tuple.\n"
-    "  --materialize arg (=off)            on | off: return the joined rows (Table<JoinedTuple>).\n"
+    "  --materialize arg (=off)            on | off | all: return the joined rows (Table<JoinedTuple>);\n"
+    "                                      on: one per matching probe tuple, all: one per pair (inner join).\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
     "  --exchange arg                      rccl | local: force the multi-GPU path (rccl on one device is\n"
     "                                      an RCCL world of one; local = device copies, devices may repeat).\n";
 
-// --materialize on: the rows Run() returned (count, and a checksum of their
+// --materialize on | all: the rows Run() returned (count, and a checksum of their
 // columns so a caller can compare runs without the rows themselves)
 void report_rows(const Common::Table<Common::JoinedTuple>& rows, Common::IHashJoinTimer& timer, bool materialize) {
     if (!materialize) return;
@@ -147,6 +148,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
         if (vm.count("device")) c.GpuConfig.Device = parse_number<int>("device", vm["device"]);
         if (vm.count("materialize")) {
             if (vm["materialize"] == "on") c.GpuConfig.Materialize = true;
+            else if (vm["materialize"] == "all") c.GpuConfig.MaterializeAll = true;
             else if (vm["materialize"] != "off")
                 throw std::invalid_argument("the argument ('" + vm["materialize"] + "') for option '--materialize' is invalid");
         }
@@ -201,8 +203,9 @@ Common::Configuration parseArguments(int argc, char** argv) {
             else if (vm["exchange"] == "local") c.GpuConfig.ContextFlags = PHJ_CTX_LOCAL;
             else throw std::invalid_argument("the argument ('" + vm["exchange"] + "') for option '--exchange' is invalid");
         }
-        if (c.GpuConfig.Materialize && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
-            throw std::invalid_argument("--materialize on runs on one device");
+        if ((c.GpuConfig.Materialize || c.GpuConfig.MaterializeAll) &&
+            (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
+            throw std::invalid_argument("--materialize on / all runs on one device");
         // validateParsedConfiguration (src/Arguments.hpp:7-18)
         c.OutputConfig.Validate();
         c.OutputFormatConfig.Validate();
@@ -293,7 +296,7 @@ int main(int argc, char** argv) {
                     Gpu::NoPartitioning::HashJoiner<decltype(factory)> joiner(configuration.NoPartitioningConfig, device,
                                                                              factory, configuration.GpuConfig);
                     auto joined = tableA ? joiner.Run(tableA, tableB, timer) : joiner.RunResident(timer);
-                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize);
+                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize || configuration.GpuConfig.MaterializeAll);
                 };
                 if (configuration.GpuConfig.Hash == PHJ_HASH_MURMUR3) run(Common::Murmur3Hasher(hashSeed));
                 else run(Common::XXHasher(hashSeed));
@@ -321,7 +324,7 @@ int main(int argc, char** argv) {
                     Gpu::RadixClustering::HashJoiner<decltype(factory), H> joiner(
                         configuration.RadixClusteringConfig, device, hasher, factory, configuration.GpuConfig);
                     auto joined = tableA ? joiner.Run(tableA, tableB, timer) : joiner.RunResident(timer);
-                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize);
+                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize || configuration.GpuConfig.MaterializeAll);
                 };
                 if (configuration.GpuConfig.Hash == PHJ_HASH_MURMUR3) run(Common::Murmur3Hasher(hashSeed));
                 else run(Common::XXHasher(hashSeed));
