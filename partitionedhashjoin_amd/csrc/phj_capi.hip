@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -77,6 +78,13 @@ struct Tuning {
     int cl_cap = static_cast<int>(kClCapMax);   // ... LDS table slots (8192: two workgroups per CU, 16384: one)
     int cl_bits = 0;      // ... clusters = 2^cl_bits (0: the fewest >= 256 whose average fits the table)
 };
+
+// f(std::integral_constant<int, HK>) for the hash kind hk: a kernel template
+// over the hash is named once per launch site, as <decltype(h)::value>.
+template <class F>
+auto with_hash(int hk, F f) {
+    return hk == kMurmur3 ? f(std::integral_constant<int, kMurmur3>{}) : f(std::integral_constant<int, kXXH3>{});
+}
 
 int env_int(const char* name, int dflt) {
     const char* v = std::getenv(name);
@@ -705,33 +713,36 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                         // keeps one tile in flight, which also gives it a kernel name of
                         // its own in rocprof summaries (S's is the roofline kernel)
                         const int kpf = prefix.rfind("R.", 0) == 0 ? 1 : 2;
-                        kfn = hk == kMurmur3 ? (dpt == 4 ? pipe1024<kMurmur3, 2>(kpf) : pipe1024<kMurmur3, 1>(kpf))
-                                             : (dpt == 4 ? pipe1024<kXXH3, 2>(kpf) : pipe1024<kXXH3, 1>(kpf));
-                    } else if (hk == kMurmur3)
-                        kfn = dpt == 4 ? reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, kMurmur3, 4>)
-                            : dpt == 2 ? reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, kMurmur3, 2>)
-                                       : reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, kMurmur3, 1>);
-                    else
-                        kfn = dpt == 4 ? reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, kXXH3, 4>)
-                            : dpt == 2 ? reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, kXXH3, 2>)
-                                       : reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, kXXH3, 1>);
+                        kfn = with_hash(hk, [&](auto h) {
+                            constexpr int HK = decltype(h)::value;
+                            return dpt == 4 ? pipe1024<HK, 2>(kpf) : pipe1024<HK, 1>(kpf);
+                        });
+                    } else
+                        kfn = with_hash(hk, [&](auto h) {
+                            constexpr int HK = decltype(h)::value;
+                            return dpt == 4 ? reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, HK, 4>)
+                                 : dpt == 2 ? reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, HK, 2>)
+                                            : reinterpret_cast<const void*>(&k_chunk_codes_pipe<BLOCK, ITEMS, HK, 1>);
+                        });
                 }
             } else if (a.keys_only) {
                 if constexpr (BLOCK == 512 && ITEMS == 8) {
-                    if (a.nbins > 2 * BLOCK)
-                        kfn = hk == kMurmur3 ? reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, kMurmur3, 4>)
-                                             : reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, kXXH3, 4>);
-                    else if (a.nbins > BLOCK)
-                        kfn = hk == kMurmur3 ? reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, kMurmur3, 2>)
-                                             : reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, kXXH3, 2>);
+                    if (a.nbins > BLOCK)
+                        kfn = with_hash(hk, [&](auto h) {
+                            constexpr int HK = decltype(h)::value;
+                            return a.nbins > 2 * BLOCK ? reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, HK, 4>)
+                                                       : reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, HK, 2>);
+                        });
                 }
                 if (!kfn && a.nbins > BLOCK) return set_err(c, PHJ_ERR_INVALID, "keys-only pass 1: more digits than threads");
                 if (!kfn)
-                    kfn = hk == kMurmur3 ? reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, kMurmur3>)
-                                         : reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, kXXH3>);
+                    kfn = with_hash(hk, [](auto h) {
+                        return reinterpret_cast<const void*>(&k_chunk_codes<BLOCK, ITEMS, decltype(h)::value>);
+                    });
             } else
-                kfn = hk == kMurmur3 ? reinterpret_cast<const void*>(&k_scatter_chunked<BLOCK, ITEMS, kMurmur3, 3>)
-                                     : reinterpret_cast<const void*>(&k_scatter_chunked<BLOCK, ITEMS, kXXH3, 3>);
+                kfn = with_hash(hk, [](auto h) {
+                    return reinterpret_cast<const void*>(&k_scatter_chunked<BLOCK, ITEMS, decltype(h)::value, 3>);
+                });
             // workgroups per CU: what the LDS and the kernel's registers allow
             // (cached per kernel and LDS size; one cache per worker thread)
             const int occ = std::max(1, occupancy(kfn, kblock, lds));
@@ -786,21 +797,19 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
             hipLaunchKernelGGL((k_hist_col<T, uint16_t>), dim3(cgrid), dim3(256), clds, c->ks, ac);
         else
             hipLaunchKernelGGL((k_hist_col<T, uint8_t>), dim3(cgrid), dim3(256), clds, c->ks, ac);
-    } else if (hk == kMurmur3)
-        hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, IN_AOS, kMurmur3>), dim3(grid), dim3(BLOCK), hist_lds, c->ks, a);
-    else
-        hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, IN_AOS, kXXH3>), dim3(grid), dim3(BLOCK), hist_lds, c->ks, a);
+    } else
+        with_hash(hk, [&](auto h) {
+            hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, IN_AOS, decltype(h)::value>), dim3(grid), dim3(BLOCK), hist_lds, c->ks, a);
+        });
     PHJ_LAUNCHED(c, hname);
     PHJ_TRY(timer_end(c));
     PHJ_TRY(timer_begin(c, cname.c_str(), static_cast<uint64_t>(hist_len) * 12));
     PHJ_TRY(scan_u32(c, a.hist, hist_len, 1, hist_len, c->scan_scratch));
     PHJ_TRY(timer_end(c));
     PHJ_TRY(timer_begin(c, sname.c_str(), n * 32 + (a.out_dig ? n * (a.dig_wide ? 2 : 1) : 0)));
-    if (hk == kMurmur3) {
-        hipLaunchKernelGGL((k_scatter<BLOCK, ITEMS, IN_AOS, OUT_AOS, kMurmur3>), dim3(grid), dim3(BLOCK), sc_lds, c->ks, a);
-    } else {
-        hipLaunchKernelGGL((k_scatter<BLOCK, ITEMS, IN_AOS, OUT_AOS, kXXH3>), dim3(grid), dim3(BLOCK), sc_lds, c->ks, a);
-    }
+    with_hash(hk, [&](auto h) {
+        hipLaunchKernelGGL((k_scatter<BLOCK, ITEMS, IN_AOS, OUT_AOS, decltype(h)::value>), dim3(grid), dim3(BLOCK), sc_lds, c->ks, a);
+    });
     PHJ_LAUNCHED(c, sname);
     PHJ_TRY(timer_end(c));
     return PHJ_OK;
@@ -1141,8 +1150,9 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
         fa.count = static_cast<unsigned long long*>(c->count.p);
         fa.cycles = static_cast<unsigned long long*>(c->split.p);
         fa.seed = pl.seed;
-        const void* kfn = pl.hk == kMurmur3 ? reinterpret_cast<const void*>(&k_join_fused<kMurmur3, kFusedKPL, kFusedTcap>)
-                                            : reinterpret_cast<const void*>(&k_join_fused<kXXH3, kFusedKPL, kFusedTcap>);
+        const void* kfn = with_hash(pl.hk, [](auto h) {
+            return reinterpret_cast<const void*>(&k_join_fused<decltype(h)::value, kFusedKPL, kFusedTcap>);
+        });
         int per_cu = 0;
         if ((per_cu = occupancy(kfn, kBlock, 0)) < 1) per_cu = 2;
         const size_t wblocks = (nslots + kWaves - 1) / kWaves;
@@ -1194,8 +1204,9 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
         PHJ_TRY(scan_u32(c, static_cast<uint32_t*>(c->prep.p), P + 1, 1, P + 1));
         if (nR) {
             const dim3 bg(static_cast<uint32_t>((nR + kBlock - 1) / kBlock));
-            if (pl.hk == kMurmur3) hipLaunchKernelGGL((k_pt_build<kMurmur3>), bg, dim3(kBlock), 0, c->ks, ta);
-            else hipLaunchKernelGGL((k_pt_build<kXXH3>), bg, dim3(kBlock), 0, c->ks, ta);
+            with_hash(pl.hk, [&](auto h) {
+                hipLaunchKernelGGL((k_pt_build<decltype(h)::value>), bg, dim3(kBlock), 0, c->ks, ta);
+            });
             PHJ_LAUNCHED(c, "k_pt_build");
         }
         PHJ_TRY(timer_end(c));
@@ -1208,12 +1219,10 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
             auto* cnt = static_cast<unsigned long long*>(c->count.p);
             const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
             const auto* tob = static_cast<const uint32_t*>(c->prep.p);
-            if (pl.hk == kMurmur3)
-                hipLaunchKernelGGL((k_pt_probe<kMurmur3, IT>), pg, dim3(kBlock), 0, c->ks, PS.view.keys,
+            with_hash(pl.hk, [&](auto h) {
+                hipLaunchKernelGGL((k_pt_probe<decltype(h)::value, IT>), pg, dim3(kBlock), 0, c->ks, PS.view.keys,
                                    static_cast<uint32_t>(nS), tab, tob, ta.f, pl.seed, cnt);
-            else
-                hipLaunchKernelGGL((k_pt_probe<kXXH3, IT>), pg, dim3(kBlock), 0, c->ks, PS.view.keys,
-                                   static_cast<uint32_t>(nS), tab, tob, ta.f, pl.seed, cnt);
+            });
             PHJ_LAUNCHED(c, "k_pt_probe");
         }
         PHJ_TRY(timer_end(c));
@@ -1277,17 +1286,15 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
     ba.ocap = ocap_wave;
     const uint32_t sgrid = (P + kWaves - 1) / kWaves;   // one wave per partition
     const size_t slds = static_cast<size_t>(ocap_wave) * 4 * kWaves;
-    if (pl.hk == kMurmur3)
-        hipLaunchKernelGGL((k_build_small<kMurmur3, kBuildKPL>), dim3(sgrid), dim3(kBlock), slds, c->ks, ba);
-    else
-        hipLaunchKernelGGL((k_build_small<kXXH3, kBuildKPL>), dim3(sgrid), dim3(kBlock), slds, c->ks, ba);
+    with_hash(pl.hk, [&](auto h) {
+        hipLaunchKernelGGL((k_build_small<decltype(h)::value, kBuildKPL>), dim3(sgrid), dim3(kBlock), slds, c->ks, ba);
+    });
     PHJ_LAUNCHED(c, "k_build_small");
     ba.ocap = ocap_build;
     const size_t blds = 64 + static_cast<size_t>(ocap_build) * 4;
-    if (pl.hk == kMurmur3)
-        hipLaunchKernelGGL((k_build_big<kMurmur3>), dim3(256), dim3(kBlock), blds, c->ks, ba);
-    else
-        hipLaunchKernelGGL((k_build_big<kXXH3>), dim3(256), dim3(kBlock), blds, c->ks, ba);
+    with_hash(pl.hk, [&](auto h) {
+        hipLaunchKernelGGL((k_build_big<decltype(h)::value>), dim3(256), dim3(kBlock), blds, c->ks, ba);
+    });
     PHJ_LAUNCHED(c, "k_build_big");
     PHJ_TRY(timer_end(c));
     PHJ_TRY(mark(c, e_build1));
@@ -1305,15 +1312,12 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
     // staged table slice per item: 512 keys (2 per lane) covers |R|/P up to ~300
     // (P = 65536 at 10M); larger per-partition tables stage 2048 keys or probe in place
     const bool small = expect * 2 <= 512;
-    const void* kfn = nullptr;
-#define PHJ_PROBE_PICK(HK_, IT_, KPT_) kfn = reinterpret_cast<const void*>(&k_probe<HK_, IT_, KPT_>)
-    if (pl.hk == kMurmur3) { if (small) PHJ_PROBE_PICK(kMurmur3, 8, 2); else PHJ_PROBE_PICK(kMurmur3, 8, 8); }
-    else { if (small) PHJ_PROBE_PICK(kXXH3, 8, 2); else PHJ_PROBE_PICK(kXXH3, 8, 8); }
-#undef PHJ_PROBE_PICK
-    if (wave_probe) {
-        if (pl.hk == kMurmur3) kfn = reinterpret_cast<const void*>(&k_probe_wave<kMurmur3, kProbeWaveKPL, kProbeWaveTcap>);
-        else kfn = reinterpret_cast<const void*>(&k_probe_wave<kXXH3, kProbeWaveKPL, kProbeWaveTcap>);
-    }
+    const void* kfn = with_hash(pl.hk, [&](auto h) {
+        constexpr int HK = decltype(h)::value;
+        return wave_probe ? reinterpret_cast<const void*>(&k_probe_wave<HK, kProbeWaveKPL, kProbeWaveTcap>)
+             : small      ? reinterpret_cast<const void*>(&k_probe<HK, 8, 2>)
+                          : reinterpret_cast<const void*>(&k_probe<HK, 8, 8>);
+    });
     int per_cu = 0;
     if ((per_cu = occupancy(kfn, kBlock, 0)) < 1) per_cu = 2;
     const size_t item_blocks = wave_probe ? (item_bound + kWaves - 1) / kWaves : item_bound;
@@ -1366,8 +1370,9 @@ int partition_build(phj_ctx* c, const Plan& pl, int64_t* out, uint32_t* bounds) 
     const uint32_t grid = (nt + 7) & ~7u;
     const size_t hlds = static_cast<size_t>(BLOCK / 64) * nb * 4;
     PHJ_TRY(timer_begin(c, "R.p1.hist", static_cast<uint64_t>(n) * 16));
-    if (pl.hk == kMurmur3) hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, true, kMurmur3>), dim3(grid), dim3(BLOCK), hlds, c->ks, a);
-    else hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, true, kXXH3>), dim3(grid), dim3(BLOCK), hlds, c->ks, a);
+    with_hash(pl.hk, [&](auto h) {
+        hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, true, decltype(h)::value>), dim3(grid), dim3(BLOCK), hlds, c->ks, a);
+    });
     PHJ_LAUNCHED(c, "k_hist");
     PHJ_TRY(timer_end(c));
     PHJ_TRY(timer_begin(c, "R.p1.scan", static_cast<uint64_t>(hlen) * 12));
@@ -1376,10 +1381,9 @@ int partition_build(phj_ctx* c, const Plan& pl, int64_t* out, uint32_t* bounds) 
     // algorithmic bytes: the 16-B tuple read, the 8-B code written
     PHJ_TRY(timer_begin(c, "R.p1.scatter", static_cast<uint64_t>(n) * 24));
     const size_t slds = scatter_codes_lds_bytes(T, nb);
-    if (pl.hk == kMurmur3)
-        hipLaunchKernelGGL((k_scatter_codes<BLOCK, ITEMS, kMurmur3>), dim3(grid), dim3(BLOCK), slds, c->ks, a);
-    else
-        hipLaunchKernelGGL((k_scatter_codes<BLOCK, ITEMS, kXXH3>), dim3(grid), dim3(BLOCK), slds, c->ks, a);
+    with_hash(pl.hk, [&](auto h) {
+        hipLaunchKernelGGL((k_scatter_codes<BLOCK, ITEMS, decltype(h)::value>), dim3(grid), dim3(BLOCK), slds, c->ks, a);
+    });
     PHJ_LAUNCHED(c, "k_scatter_codes");
     PHJ_TRY(timer_end(c));
     if (pl.cluster) {   // the cluster bounds from the scanned histogram
@@ -1491,8 +1495,9 @@ int probe_ht(phj_ctx* c, const Plan& pl, SideState& PS, bool clear = true) {
     const bool radix = pl.mode == 0 && pl.sub_bits == 0;
     const void* kfn = PS.hcoded ? (radix ? reinterpret_cast<const void*>(&k_probe_ht<B, I, kHashed, kProbeRadix | kProbeChunked>)
                                          : reinterpret_cast<const void*>(&k_probe_ht<B, I, kHashed, kProbeChunked>))
-                      : pl.hk == kMurmur3 ? reinterpret_cast<const void*>(&k_probe_ht<B, I, kMurmur3>)
-                                          : reinterpret_cast<const void*>(&k_probe_ht<B, I, kXXH3>);
+                      : with_hash(pl.hk, [](auto h) {
+                            return reinterpret_cast<const void*>(&k_probe_ht<B, I, decltype(h)::value>);
+                        });
     // persistent: as many workgroups as fit the chip at once (a multiple of 8:
     // XCD x owns tiles [x, x + 1) * ntiles / 8), never many more than tiles
     int per_cu = 0;
@@ -1781,8 +1786,9 @@ int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         // algorithmic bytes: S's tuples read once (16 B), R's tables (~2 slots per code) once
         PHJ_TRY(timer_begin(c, "np.probe", S.n * 16 + R.n * 16));
         constexpr int IT = 4;
-        const void* kfn = p->hash == PHJ_HASH_MURMUR3 ? reinterpret_cast<const void*>(&k_np_probe_ct<kMurmur3, IT>)
-                                                      : reinterpret_cast<const void*>(&k_np_probe_ct<kXXH3, IT>);
+        const void* kfn = with_hash(p->hash, [](auto h) {
+            return reinterpret_cast<const void*>(&k_np_probe_ct<decltype(h)::value, IT>);
+        });
         int per_cu = 0;
         if ((per_cu = occupancy(kfn, 256, 0)) < 1) per_cu = 8;
         const uint64_t want = (S.n + 256ull * IT - 1) / (256ull * IT);
@@ -1870,12 +1876,10 @@ int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipE
         auto* tab = static_cast<NPBucket*>(c->np_tab.p);
         auto* pays = static_cast<int64_t*>(c->np_pays.p);
         const dim3 grid(1u << g.rbits);
-        if (p->hash == PHJ_HASH_MURMUR3)
-            hipLaunchKernelGGL((k_np_build_region<kMurmur3>), grid, dim3(kBlock), lds, c->ks, v.keys, v.payloads,
-                               v.bounds, g, tab, pays, p->hash_seed, ovn, ov, ovb);
-        else
-            hipLaunchKernelGGL((k_np_build_region<kXXH3>), grid, dim3(kBlock), lds, c->ks, v.keys, v.payloads,
-                               v.bounds, g, tab, pays, p->hash_seed, ovn, ov, ovb);
+        with_hash(p->hash, [&](auto h) {
+            hipLaunchKernelGGL((k_np_build_region<decltype(h)::value>), grid, dim3(kBlock), lds, c->ks, v.keys,
+                               v.payloads, v.bounds, g, tab, pays, p->hash_seed, ovn, ov, ovb);
+        });
         PHJ_LAUNCHED(c, "k_np_build_region");
         hipLaunchKernelGGL(k_np_build_overflow, dim3(64), dim3(kBlock), 0, c->ks, ovn, ov, ovb, tab, pays, nb);
         PHJ_LAUNCHED(c, "k_np_build_overflow");
@@ -1914,16 +1918,15 @@ int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32
         // probe serves larger build sides and, with marks, the materialised join)
         if (marks) {
             const uint32_t mg = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
-            if (p->hash == PHJ_HASH_MURMUR3)
-                hipLaunchKernelGGL((k_np_probe_mark<kMurmur3>), dim3(mg), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, g,
-                                   p->hash_seed, marks, cnt);
-            else
-                hipLaunchKernelGGL((k_np_probe_mark<kXXH3>), dim3(mg), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, g,
-                                   p->hash_seed, marks, cnt);
-        } else if (p->hash == PHJ_HASH_MURMUR3) {
-            hipLaunchKernelGGL((k_np_probe<kMurmur3, 4, 1>), dim3(pg), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, g, p->hash_seed, cnt);
+            with_hash(p->hash, [&](auto h) {
+                hipLaunchKernelGGL((k_np_probe_mark<decltype(h)::value>), dim3(mg), dim3(kBlock), 0, c->ks, S_rel, S.n,
+                                   tab, g, p->hash_seed, marks, cnt);
+            });
         } else {
-            hipLaunchKernelGGL((k_np_probe<kXXH3, 4, 1>), dim3(pg), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, g, p->hash_seed, cnt);
+            with_hash(p->hash, [&](auto h) {
+                hipLaunchKernelGGL((k_np_probe<decltype(h)::value, 4, 1>), dim3(pg), dim3(kBlock), 0, c->ks, S_rel, S.n,
+                                   tab, g, p->hash_seed, cnt);
+            });
         }
         PHJ_LAUNCHED(c, "k_np_probe");
         PHJ_TRY(timer_end(c));
@@ -1984,33 +1987,41 @@ int mat_compact(phj_ctx* c, uint64_t nS, const longlong2* s_aos, const int64_t* 
     return timer_end(c);
 }
 
-int join_radix_mark(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
+// The radix forms of the materialised join and of the inner join (the fused
+// per-partition LDS join of both sides fully partitioned, SoA): what they
+// share before their first join kernel (fused_setup, fused_items) and at
+// their end (fused_times).
+struct FusedJoin {
     Plan pl;
-    PHJ_TRY(make_plan(c, p, pl));
+    uint32_t requested = 0;   // partitions asked for (pl may be refined)
+    uint64_t nS = 0;          // partitioned probe tuples: mat_mark has one word each
+    hipEvent_t t0 = nullptr, t1 = nullptr;   // around the partitioning
+    FusedArgs fa{};
+    uint32_t grid = 0;
+};
+
+// Plan, precondition ("<what> needs ..."), both sides partitioned, the
+// workspace sized, the count cleared, the join kernels' arguments and grid.
+int fused_setup(phj_ctx* c, const phj_join_params* p, const char* what, FusedJoin& j) {
+    PHJ_TRY(make_plan(c, p, j.pl));
     SideState& R = c->side[PHJ_SIDE_BUILD];
     SideState& S = c->side[PHJ_SIDE_PROBE];
-    const uint32_t requested = pl.Ppad;
-    refine_plan(c, pl, R.n);
-    const uint32_t P = pl.Ppad;
+    j.requested = j.pl.Ppad;
+    refine_plan(c, j.pl, R.n);
+    const uint32_t P = j.pl.Ppad;
     if (!c->tune.fused || (R.n + P - 1) / P * 3 > static_cast<uint64_t>(kFusedTcap) * 2)
-        return set_err(c, PHJ_ERR_INVALID, "materialised radix join needs the fused LDS join (PHJ_FUSED, PHJ_SUBPART)");
-    hipEvent_t t0, t1, p1;
-    PHJ_TRY(mark(c, &t0));
-    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl));
-    PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, pl));
-    PHJ_TRY(mark(c, &t1));
-    const uint64_t nS = S.view.n;
-    const size_t nslots = nS / kFusedChunk + P + 1;
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + " needs the fused LDS join (PHJ_FUSED, PHJ_SUBPART)");
+    PHJ_TRY(mark(c, &j.t0));
+    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, j.pl));
+    PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, j.pl));
+    PHJ_TRY(mark(c, &j.t1));
+    j.nS = S.view.n;
+    const size_t nslots = j.nS / kFusedChunk + P + 1;
     PHJ_TRY(ensure(c, c->fitems, nslots * sizeof(FusedItem)));
     PHJ_TRY(ensure(c, c->count, 32));
-    PHJ_TRY(ensure(c, c->mat_mark, std::max<uint64_t>(1, nS) * 4));
+    PHJ_TRY(ensure(c, c->mat_mark, j.nS * 4));
     PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
-    PHJ_HIP(c, hipMemsetAsync(c->mat_mark.p, 0xff, std::max<uint64_t>(1, nS) * 4, c->ks));
-    PHJ_TRY(timer_begin(c, "mat.join", R.n * 8 + nS * 12));
-    hipLaunchKernelGGL(k_fused_items, dim3((P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, S.view.bounds, P,
-                       static_cast<FusedItem*>(c->fitems.p));
-    PHJ_LAUNCHED(c, "k_fused_items");
-    FusedArgs fa{};
+    FusedArgs& fa = j.fa;
     fa.L.nseg = 1;
     fa.L.P = P;
     fa.L.seg[0].keys = R.view.keys;
@@ -2021,27 +2032,52 @@ int join_radix_mark(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     fa.items = static_cast<const FusedItem*>(c->fitems.p);
     fa.nitems = static_cast<uint32_t>(nslots - 1);
     fa.count = static_cast<unsigned long long*>(c->count.p);
-    fa.seed = pl.seed;
-    const uint32_t grid = static_cast<uint32_t>(
+    fa.seed = j.pl.seed;
+    j.grid = static_cast<uint32_t>(
         std::max<size_t>(1, std::min<size_t>((nslots + kWaves - 1) / kWaves, static_cast<size_t>(4) * c->num_cus)));
+    return PHJ_OK;
+}
+
+// Opens the first join kernel's timer (it reads the build keys and the probe
+// keys and writes a word per probe tuple) with the work items inside it.
+int fused_items(phj_ctx* c, const char* timer, const FusedJoin& j) {
+    PHJ_TRY(timer_begin(c, timer, c->side[PHJ_SIDE_BUILD].n * 8 + j.nS * 12));
+    hipLaunchKernelGGL(k_fused_items, dim3((j.fa.L.P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, j.fa.sbounds,
+                       j.fa.L.P, static_cast<FusedItem*>(c->fitems.p));
+    PHJ_LAUNCHED(c, "k_fused_items");
+    return PHJ_OK;
+}
+
+// p1: the event behind the join's last kernel.
+int fused_times(phj_ctx* c, const FusedJoin& j, hipEvent_t p1, phj_join_result* r) {
+    r->partition_ms = elapsed(c, j.t0, j.t1);
+    r->probe_ms = elapsed(c, j.t1, p1);
+    r->total_ms = elapsed(c, j.t0, p1);
+    return fill_timers(c, r);
+}
+
+int join_radix_mark(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
+    FusedJoin j;
+    PHJ_TRY(fused_setup(c, p, "materialised radix join", j));
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    const SideState& S = c->side[PHJ_SIDE_PROBE];
     auto* mk = static_cast<uint32_t*>(c->mat_mark.p);
-    if (pl.hk == kMurmur3)
-        hipLaunchKernelGGL(k_join_fused_mark<kMurmur3>, dim3(grid), dim3(kBlock), 0, c->ks, fa, mk);
-    else
-        hipLaunchKernelGGL(k_join_fused_mark<kXXH3>, dim3(grid), dim3(kBlock), 0, c->ks, fa, mk);
+    PHJ_HIP(c, hipMemsetAsync(mk, 0xff, std::max<uint64_t>(1, j.nS) * 4, c->ks));
+    PHJ_TRY(fused_items(c, "mat.join", j));
+    with_hash(j.pl.hk, [&](auto h) {
+        hipLaunchKernelGGL(k_join_fused_mark<decltype(h)::value>, dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, mk);
+    });
     PHJ_LAUNCHED(c, "k_join_fused_mark");
     PHJ_TRY(timer_end(c));
-    PHJ_TRY(mat_compact(c, nS, nullptr, S.view.keys, S.view.payloads, R.view.payloads));
+    PHJ_TRY(mat_compact(c, j.nS, nullptr, S.view.keys, S.view.payloads, R.view.payloads));
+    hipEvent_t p1;
     PHJ_TRY(mark(c, &p1));
     uint64_t m = 0;
     PHJ_TRY(get_count(c, &m));
     r->matches = m;
-    r->partition_ms = elapsed(c, t0, t1);
-    r->probe_ms = elapsed(c, t1, p1);
-    r->total_ms = elapsed(c, t0, p1);
-    r->num_partitions = requested;
-    r->algorithmic_bytes = partition_bytes(pl, R.n) + partition_bytes(pl, S.n) + R.n * 8 + nS * 12 + m * 24;
-    return fill_timers(c, r);
+    r->num_partitions = j.requested;
+    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n) + R.n * 8 + j.nS * 12 + m * 24;
+    return fused_times(c, j, p1, r);
 }
 
 // ---- the inner join (phj_inner.h): count, offsets, emit ----
@@ -2074,8 +2110,31 @@ int inner_offsets(phj_ctx* c, uint64_t nS) {
 // the emit pass reads the build keys, the probe tuples and pairs[] again and,
 // per row, gathers a build payload and writes 24 B.
 uint64_t inner_count_bytes(uint64_t nR, uint64_t nS) { return nR * 8 + nS * (8 + 4); }
-uint64_t inner_emit_bytes(uint64_t nR, uint64_t nS, uint64_t rows) {
-    return nS * 12 + nR * 8 + nS * (16 + 4) + rows * (8 + 24);
+uint64_t inner_emit_bytes(uint64_t nS, uint64_t rows) {   // (without the build side)
+    return nS * 12 + nS * (16 + 4) + rows * (8 + 24);
+}
+
+// Passes 2 and 3 after a count of r->matches pairs over nS probe tuples:
+// the row limit, the workspace, then offsets and launch(rows) (the join again,
+// emitting) in the "inner.emit" timer; *end: the event behind it. build_bytes:
+// what the emit pass reads of the build side (its keys, or the bucket table).
+template <class F>
+int inner_emit(phj_ctx* c, phj_join_result* r, uint64_t nS, uint64_t build_bytes, hipEvent_t* end, F launch) {
+    const uint64_t m = r->matches;
+    // nothing is written and the row buffer is not grown above the limit
+    if (m >= kInnerRowLimit) return inner_range_error(c, m);
+    const uint32_t nblk = static_cast<uint32_t>((nS + kMatBlock - 1) / kMatBlock);
+    PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
+    PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, m) * sizeof(JoinedRow)));
+    const uint64_t bytes = inner_emit_bytes(nS, m) + build_bytes;
+    PHJ_TRY(timer_begin(c, "inner.emit", bytes));
+    PHJ_TRY(inner_offsets(c, nS));
+    PHJ_TRY(launch(static_cast<JoinedRow*>(c->mat_rows.p)));
+    PHJ_TRY(timer_end(c));
+    PHJ_TRY(mark(c, end));
+    PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    r->algorithmic_bytes += bytes;
+    return PHJ_OK;
 }
 
 int join_nopart_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit) {
@@ -2098,41 +2157,26 @@ int join_nopart_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, 
     auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
     auto* cnt = static_cast<unsigned long long*>(c->count.p);
     const uint64_t table_bytes = static_cast<uint64_t>(g.nb) * 64;
+    auto launch = [&](auto e, JoinedRow* rows, uint32_t nrows) -> int {
+        with_hash(p->hash, [&](auto h) {
+            hipLaunchKernelGGL((k_np_inner<decltype(h)::value, decltype(e)::value>), dim3(grid), dim3(kBlock), 0, c->ks,
+                               S_rel, S.n, tab, pays, g, p->hash_seed, pairs, cnt, rows, nrows);
+        });
+        PHJ_LAUNCHED(c, "k_np_inner");
+        return PHJ_OK;
+    };
     PHJ_TRY(timer_begin(c, "inner.count", inner_count_bytes(0, S.n) + table_bytes));
-    if (p->hash == PHJ_HASH_MURMUR3)
-        hipLaunchKernelGGL((k_np_inner<kMurmur3, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
-                           g, p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
-    else
-        hipLaunchKernelGGL((k_np_inner<kXXH3, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
-                           p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
-    PHJ_LAUNCHED(c, "k_np_inner");
+    PHJ_TRY(launch(std::false_type{}, nullptr, 0u));
     PHJ_TRY(timer_end(c));
     PHJ_TRY(mark(c, &e2));
     uint64_t m = 0;
     PHJ_TRY(get_count(c, &m));
     r->matches = m;
     r->algorithmic_bytes = R.n * 32 + table_bytes + inner_count_bytes(0, S.n) + table_bytes;
-    if (emit) {
-        // nothing is written and the row buffer is not grown above the limit
-        if (m >= kInnerRowLimit) return inner_range_error(c, m);
-        const uint32_t nblk = static_cast<uint32_t>((S.n + kMatBlock - 1) / kMatBlock);
-        PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
-        PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, m) * sizeof(JoinedRow)));
-        auto* rows = static_cast<JoinedRow*>(c->mat_rows.p);
-        PHJ_TRY(timer_begin(c, "inner.emit", inner_emit_bytes(0, S.n, m) + table_bytes));
-        PHJ_TRY(inner_offsets(c, S.n));
-        if (p->hash == PHJ_HASH_MURMUR3)
-            hipLaunchKernelGGL((k_np_inner<kMurmur3, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
-                               g, p->hash_seed, pairs, cnt, rows, static_cast<uint32_t>(m));
-        else
-            hipLaunchKernelGGL((k_np_inner<kXXH3, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
-                               g, p->hash_seed, pairs, cnt, rows, static_cast<uint32_t>(m));
-        PHJ_LAUNCHED(c, "k_np_inner");
-        PHJ_TRY(timer_end(c));
-        PHJ_TRY(mark(c, &e2));
-        PHJ_HIP(c, hipStreamSynchronize(c->ks));
-        r->algorithmic_bytes += inner_emit_bytes(0, S.n, m) + table_bytes;
-    }
+    if (emit)
+        PHJ_TRY(inner_emit(c, r, S.n, table_bytes, &e2, [&](JoinedRow* rows) {
+            return launch(std::true_type{}, rows, static_cast<uint32_t>(m));
+        }));
     r->partition_ms = 0;
     r->build_ms = elapsed(c, e0, e1);
     r->probe_ms = elapsed(c, e1, e2);
@@ -2144,86 +2188,36 @@ int join_nopart_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, 
 // The radix form: both sides fully partitioned (SoA), then the per-partition
 // LDS join twice (join_radix_mark's precondition: the fused LDS join).
 int join_radix_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit) {
-    Plan pl;
-    PHJ_TRY(make_plan(c, p, pl));
-    SideState& R = c->side[PHJ_SIDE_BUILD];
-    SideState& S = c->side[PHJ_SIDE_PROBE];
-    const uint32_t requested = pl.Ppad;
-    refine_plan(c, pl, R.n);
-    const uint32_t P = pl.Ppad;
-    if (!c->tune.fused || (R.n + P - 1) / P * 3 > static_cast<uint64_t>(kFusedTcap) * 2)
-        return set_err(c, PHJ_ERR_INVALID, "radix inner join needs the fused LDS join (PHJ_FUSED, PHJ_SUBPART)");
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    const SideState& S = c->side[PHJ_SIDE_PROBE];
     if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
     if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
-    hipEvent_t t0, t1, p1;
-    PHJ_TRY(mark(c, &t0));
-    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl));
-    PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, pl));
-    PHJ_TRY(mark(c, &t1));
-    const uint64_t nS = S.view.n;
-    const size_t nslots = nS / kFusedChunk + P + 1;
-    PHJ_TRY(ensure(c, c->fitems, nslots * sizeof(FusedItem)));
-    PHJ_TRY(ensure(c, c->count, 32));
-    PHJ_TRY(ensure(c, c->mat_mark, nS * 4));
-    PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
-    PHJ_TRY(timer_begin(c, "inner.count", inner_count_bytes(R.n, nS)));
-    hipLaunchKernelGGL(k_fused_items, dim3((P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, S.view.bounds, P,
-                       static_cast<FusedItem*>(c->fitems.p));
-    PHJ_LAUNCHED(c, "k_fused_items");
-    FusedArgs fa{};
-    fa.L.nseg = 1;
-    fa.L.P = P;
-    fa.L.seg[0].keys = R.view.keys;
-    fa.L.seg[0].pays = R.view.payloads;
-    fa.L.seg[0].bounds = R.view.bounds;
-    fa.skeys = S.view.keys;
-    fa.sbounds = S.view.bounds;
-    fa.items = static_cast<const FusedItem*>(c->fitems.p);
-    fa.nitems = static_cast<uint32_t>(nslots - 1);
-    fa.count = static_cast<unsigned long long*>(c->count.p);
-    fa.seed = pl.seed;
-    const uint32_t grid = static_cast<uint32_t>(
-        std::max<size_t>(1, std::min<size_t>((nslots + kWaves - 1) / kWaves, static_cast<size_t>(4) * c->num_cus)));
+    FusedJoin j;
+    PHJ_TRY(fused_setup(c, p, "radix inner join", j));
     auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
-    if (pl.hk == kMurmur3)
-        hipLaunchKernelGGL((k_inner_fused<kMurmur3, false>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
-                           S.view.payloads, static_cast<JoinedRow*>(nullptr), 0u);
-    else
-        hipLaunchKernelGGL((k_inner_fused<kXXH3, false>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
-                           S.view.payloads, static_cast<JoinedRow*>(nullptr), 0u);
-    PHJ_LAUNCHED(c, "k_inner_fused");
+    auto launch = [&](auto e, JoinedRow* rows, uint32_t nrows) -> int {
+        with_hash(j.pl.hk, [&](auto h) {
+            hipLaunchKernelGGL((k_inner_fused<decltype(h)::value, decltype(e)::value>), dim3(j.grid), dim3(kBlock), 0,
+                               c->ks, j.fa, pairs, S.view.payloads, rows, nrows);
+        });
+        PHJ_LAUNCHED(c, "k_inner_fused");
+        return PHJ_OK;
+    };
+    PHJ_TRY(fused_items(c, "inner.count", j));
+    PHJ_TRY(launch(std::false_type{}, nullptr, 0u));
     PHJ_TRY(timer_end(c));
+    hipEvent_t p1;
     PHJ_TRY(mark(c, &p1));
     uint64_t m = 0;
     PHJ_TRY(get_count(c, &m));
     r->matches = m;
-    r->num_partitions = requested;
-    r->algorithmic_bytes = partition_bytes(pl, R.n) + partition_bytes(pl, S.n) + inner_count_bytes(R.n, nS);
-    if (emit) {
-        // nothing is written and the row buffer is not grown above the limit
-        if (m >= kInnerRowLimit) return inner_range_error(c, m);
-        const uint32_t nblk = static_cast<uint32_t>((nS + kMatBlock - 1) / kMatBlock);
-        PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
-        PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, m) * sizeof(JoinedRow)));
-        auto* rows = static_cast<JoinedRow*>(c->mat_rows.p);
-        PHJ_TRY(timer_begin(c, "inner.emit", inner_emit_bytes(R.n, nS, m)));
-        PHJ_TRY(inner_offsets(c, nS));
-        if (pl.hk == kMurmur3)
-            hipLaunchKernelGGL((k_inner_fused<kMurmur3, true>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
-                               S.view.payloads, rows, static_cast<uint32_t>(m));
-        else
-            hipLaunchKernelGGL((k_inner_fused<kXXH3, true>), dim3(grid), dim3(kBlock), 0, c->ks, fa, pairs,
-                               S.view.payloads, rows, static_cast<uint32_t>(m));
-        PHJ_LAUNCHED(c, "k_inner_fused");
-        PHJ_TRY(timer_end(c));
-        PHJ_TRY(mark(c, &p1));
-        PHJ_HIP(c, hipStreamSynchronize(c->ks));
-        r->algorithmic_bytes += inner_emit_bytes(R.n, nS, m);
-    }
-    r->partition_ms = elapsed(c, t0, t1);
-    r->probe_ms = elapsed(c, t1, p1);
-    r->total_ms = elapsed(c, t0, p1);
-    return fill_timers(c, r);
+    r->num_partitions = j.requested;
+    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n) + inner_count_bytes(R.n, j.nS);
+    if (emit)
+        PHJ_TRY(inner_emit(c, r, j.nS, R.n * 8, &p1, [&](JoinedRow* rows) {
+            return launch(std::true_type{}, rows, static_cast<uint32_t>(m));
+        }));
+    return fused_times(c, j, p1, r);
 }
 
 // phj_join_inner_count (emit = false) / phj_join_inner.
@@ -3194,10 +3188,9 @@ int phj_hash_keys(phj_ctx* c, int hash, uint64_t seed, const int64_t* keys, uint
     do {
         if (hipMemcpy(dk, keys, n * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = set_err(c, PHJ_ERR_HIP, "H2D"); break; }
         const uint32_t g = static_cast<uint32_t>((n + kBlock - 1) / kBlock);
-        if (hash == PHJ_HASH_MURMUR3)
-            hipLaunchKernelGGL((k_hash_keys<kMurmur3>), dim3(g), dim3(kBlock), 0, c->ks, static_cast<int64_t*>(dk), n, seed, static_cast<uint64_t*>(dout));
-        else
-            hipLaunchKernelGGL((k_hash_keys<kXXH3>), dim3(g), dim3(kBlock), 0, c->ks, static_cast<int64_t*>(dk), n, seed, static_cast<uint64_t*>(dout));
+        with_hash(hash, [&](auto h) {
+            hipLaunchKernelGGL((k_hash_keys<decltype(h)::value>), dim3(g), dim3(kBlock), 0, c->ks, static_cast<int64_t*>(dk), n, seed, static_cast<uint64_t*>(dout));
+        });
         if (hipGetLastError() != hipSuccess) { rc = set_err(c, PHJ_ERR_HIP, "k_hash_keys launch"); break; }
         if (hipStreamSynchronize(c->ks) != hipSuccess) { rc = set_err(c, PHJ_ERR_HIP, "sync"); break; }
         if (hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = set_err(c, PHJ_ERR_HIP, "D2H"); break; }

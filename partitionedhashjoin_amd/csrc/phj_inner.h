@@ -36,9 +36,9 @@ template <bool EMIT>
 __device__ __forceinline__ uint32_t np_bucket_pairs(const longlong2 (&q)[4], uint32_t b, int64_t key,
                                                     const int64_t* pays, int64_t pb, JoinedRow* out, uint32_t row,
                                                     uint32_t nrows) {
-    const uint32_t fill = static_cast<uint32_t>(q[3].y);
+    int64_t ks[kNPSlots];
+    const uint32_t fill = np_unpack(q, ks);
     const uint32_t c = fill < kNPSlots ? fill : kNPSlots;
-    const int64_t ks[kNPSlots] = {q[0].x, q[0].y, q[1].x, q[1].y, q[2].x, q[2].y, q[3].x};
     uint32_t n = 0;
 #pragma unroll
     for (int s = 0; s < kNPSlots; s++) {
@@ -76,23 +76,7 @@ __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_
         longlong2 t[IT];
         uint32_t b[IT];
         longlong2 q[IT][4];
-#pragma unroll
-        for (int j = 0; j < IT; j++) {
-            const uint64_t i = base + static_cast<uint64_t>(j) * kBlock + threadIdx.x;
-            if (EMIT) {
-                t[j] = i < nS ? S[i] : make_longlong2(0, 0);
-            } else {
-                t[j].x = i < nS ? __builtin_nontemporal_load(&S[i].x) : 0;
-                t[j].y = 0;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < IT; j++) {
-            b[j] = np_home_r(hash64<HK>(static_cast<uint64_t>(t[j].x), seed), g);
-            const longlong2* bp = reinterpret_cast<const longlong2*>(tab + b[j]);
-#pragma unroll
-            for (int w = 0; w < 4; w++) q[j][w] = bp[w];
-        }
+        np_probe_front<HK, EMIT>(S, nS, base, tab, g, seed, t, b, q);
 #pragma unroll
         for (int j = 0; j < IT; j++) {
             const uint64_t i = base + static_cast<uint64_t>(j) * kBlock + threadIdx.x;
@@ -118,22 +102,18 @@ __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_
         }
     }
     if (!EMIT) {
-        unsigned long long x = total;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long s = 0;
-            for (int w = 0; w < kWaves; w++) s += red[w];
-            if (s) atomicAdd(count, s);
-        }
+        total = block_sum(total, red);
+        if (total) atomicAdd(count, total);
     }
 }
 
 // Radix inner join: k_join_fused_mark's structure (one wave per (partition,
 // S chunk) item, the partition's build keys in the wave's LDS CSR table in
 // rounds of 256, each key's row in the partitioned build relation beside it).
+// The table round, its scan and the block total are written out here as in
+// k_join_fused_mark, not shared (phj_wave.h): with the round as a device
+// function the count pass on a hot build key (thousands of rounds on one
+// wave) measured 6 % slower, so this kernel's code stays as it was generated.
 // A probe key is looked up in every round and compared with its whole bucket:
 // no early exit. Its lane owns pairs[s] for the item, so the value is carried
 // from round to round in memory (64 probe keys per lane: too many for
@@ -323,23 +303,7 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
 // exclusive scan turns it into the blocks' first rows). 32-bit sums: the host
 // goes on only below 2^32 pairs in all.
 __global__ __launch_bounds__(kBlock) void k_inner_blocksum(const uint32_t* pairs, uint64_t n, uint32_t* cnt) {
-    __shared__ uint32_t red[kWaves];
-    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kMatBlock;
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kMatBlockItems; j++) {
-        const uint64_t i = base + j * kBlock + threadIdx.x;
-        c += i < n ? pairs[i] : 0u;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kWaves; w++) t += red[w];
-        cnt[blockIdx.x] = t;
-    }
+    block_sums<false>(pairs, n, cnt);
 }
 
 // pairs[i] -> first row of probe tuple i, in place: offs[block] plus the
@@ -356,12 +320,7 @@ __global__ __launch_bounds__(kBlock) void k_inner_prefix(uint32_t* pairs, uint64
         v[j] = base + j < n ? pairs[base + j] : 0u;
         sum += v[j];
     }
-    uint32_t x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= static_cast<uint32_t>(o)) x += y;
-    }
+    const uint32_t x = wave_scan_incl(sum, lane);
     if (lane == 63) wsum[wave] = x;
     __syncthreads();
     uint32_t row = offs[blockIdx.x] + x - sum;

@@ -32,6 +32,7 @@
 #include "phj_hash.h"
 #include "phj_pow.h"
 #include "phj_partition.h"
+#include "phj_wave.h"
 
 namespace phj {
 

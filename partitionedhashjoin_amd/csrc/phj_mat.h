@@ -46,6 +46,38 @@ __device__ __forceinline__ uint32_t np_lookup_slot(const NPBucket* tab, uint32_t
     return kNoMatch;
 }
 
+// The seven keys of a bucket from its four 16-B words; returns its fill word.
+__device__ __forceinline__ uint32_t np_unpack(const longlong2 (&q)[4], int64_t (&ks)[kNPSlots]) {
+    ks[0] = q[0].x, ks[1] = q[0].y, ks[2] = q[1].x, ks[3] = q[1].y, ks[4] = q[2].x, ks[5] = q[2].y, ks[6] = q[3].x;
+    return static_cast<uint32_t>(q[3].y);
+}
+
+// The front of a materialising NoPartitioning probe round (as k_np_probe):
+// IT tuples per thread from S[base] on, then every home bucket b[j] requested
+// (q[j]) before any compare. PAY: whole tuples; else the keys alone, read once.
+template <int HK, bool PAY, int IT>
+__device__ __forceinline__ void np_probe_front(const longlong2* S, uint64_t nS, uint64_t base, const NPBucket* tab,
+                                               NPHome g, uint64_t seed, longlong2 (&t)[IT], uint32_t (&b)[IT],
+                                               longlong2 (&q)[IT][4]) {
+#pragma unroll
+    for (int j = 0; j < IT; j++) {
+        const uint64_t i = base + static_cast<uint64_t>(j) * kBlock + threadIdx.x;
+        if (PAY) {
+            t[j] = i < nS ? S[i] : make_longlong2(0, 0);
+        } else {
+            t[j].x = i < nS ? __builtin_nontemporal_load(&S[i].x) : 0;
+            t[j].y = 0;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < IT; j++) {
+        b[j] = np_home_r(hash64<HK>(static_cast<uint64_t>(t[j].x), seed), g);
+        const longlong2* bp = reinterpret_cast<const longlong2*>(tab + b[j]);
+#pragma unroll
+        for (int w = 0; w < 4; w++) q[j][w] = bp[w];
+    }
+}
+
 // NoPartitioning probe with marks: match[i] = payload slot of S[i]'s key.
 template <int HK>
 __global__ __launch_bounds__(kBlock) void k_np_probe_mark(const longlong2* S, uint64_t nS, const NPBucket* tab,
@@ -56,29 +88,18 @@ __global__ __launch_bounds__(kBlock) void k_np_probe_mark(const longlong2* S, ui
     uint32_t hits = 0;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock * IT;
     for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kBlock * IT; base < nS; base += stride) {
-        int64_t k[IT];
+        longlong2 t[IT];
         uint32_t b[IT];
         longlong2 q[IT][4];
-#pragma unroll
-        for (int j = 0; j < IT; j++) {
-            const uint64_t i = base + static_cast<uint64_t>(j) * kBlock + threadIdx.x;
-            k[j] = i < nS ? __builtin_nontemporal_load(&S[i].x) : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < IT; j++) {
-            b[j] = np_home_r(hash64<HK>(static_cast<uint64_t>(k[j]), seed), g);
-            const longlong2* bp = reinterpret_cast<const longlong2*>(tab + b[j]);
-#pragma unroll
-            for (int w = 0; w < 4; w++) q[j][w] = bp[w];
-        }
+        np_probe_front<HK, false>(S, nS, base, tab, g, seed, t, b, q);
 #pragma unroll
         for (int j = 0; j < IT; j++) {
             const uint64_t i = base + static_cast<uint64_t>(j) * kBlock + threadIdx.x;
             if (i >= nS) continue;
-            const int64_t key = k[j];
-            const uint32_t fill = static_cast<uint32_t>(q[j][3].y);
+            const int64_t key = t[j].x;
+            int64_t ks[kNPSlots];
+            const uint32_t fill = np_unpack(q[j], ks);
             const uint32_t c = fill < kNPSlots ? fill : kNPSlots;
-            const int64_t ks[kNPSlots] = {q[j][0].x, q[j][0].y, q[j][1].x, q[j][1].y, q[j][2].x, q[j][2].y, q[j][3].x};
             uint32_t m = kNoMatch;
 #pragma unroll
             for (int s = kNPSlots - 1; s >= 0; s--)   // the first equal slot wins
@@ -89,16 +110,25 @@ __global__ __launch_bounds__(kBlock) void k_np_probe_mark(const longlong2* S, ui
             hits += m != kNoMatch;
         }
     }
-    uint32_t x = hits;
+    const uint32_t total = block_sum(hits, red);   // at most nS < 2^32
+    if (total) atomicAdd(count, static_cast<unsigned long long>(total));
+}
+
+// cnt[block] = the sum over the compaction block's elements of v[i] (MARKS:
+// of v[i] != kNoMatch), in 32 bits.
+template <bool MARKS>
+__device__ __forceinline__ void block_sums(const uint32_t* v, uint64_t n, uint32_t* cnt) {
+    __shared__ uint32_t red[kWaves];
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kMatBlock;
+    uint32_t c = 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWaves; w++) t += red[w];
-        if (t) atomicAdd(count, t);
+    for (uint32_t j = 0; j < kMatBlockItems; j++) {
+        const uint64_t i = base + j * kBlock + threadIdx.x;
+        const uint32_t x = i < n ? v[i] : (MARKS ? kNoMatch : 0u);   // (a select: the 16 loads go out together)
+        c += MARKS ? (x != kNoMatch ? 1u : 0u) : x;
     }
+    c = block_sum(c, red);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = c;
 }
 
 // Radix join with marks: the fused per-partition LDS join (k_join_fused's
@@ -152,12 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_join_fused_mark(FusedArgs a, uint32_
             for (uint32_t base = 0; base < nbk; base += 64) {
                 const uint32_t i = base + lane;
                 const uint32_t v = i < nbk ? lcur[i] : 0u;
-                uint32_t x = v;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t y = __shfl_up(x, o, 64);
-                    if (lane >= static_cast<uint32_t>(o)) x += y;
-                }
+                const uint32_t x = wave_scan_incl(v, lane);
                 if (i < nbk) {
                     loffs[i] = carry + x - v;
                     lcur[i] = carry + x - v;
@@ -198,38 +223,14 @@ __global__ __launch_bounds__(kBlock) void k_join_fused_mark(FusedArgs a, uint32_
         }
         hits += __popcll(hitbits);
     }
-    unsigned long long x = hits;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    if (lane == 0) red[wave] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long t = 0;
-        for (int w = 0; w < kWaves; w++) t += red[w];
-        if (t) atomicAdd(a.count, t);
-    }
+    const unsigned long long total = block_sum(hits, red);
+    if (total) atomicAdd(a.count, total);
 }
 
 // Matches per compaction block -> cnt[block] (cnt has nblocks + 1 entries; the
 // exclusive scan turns it into row offsets and the total).
 __global__ __launch_bounds__(kBlock) void k_mat_count(const uint32_t* match, uint64_t n, uint32_t* cnt) {
-    __shared__ uint32_t red[kWaves];
-    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kMatBlock;
-    uint32_t c = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kMatBlockItems; j++) {
-        const uint64_t i = base + j * kBlock + threadIdx.x;
-        c += (i < n && match[i] != kNoMatch) ? 1u : 0u;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kWaves; w++) t += red[w];
-        cnt[blockIdx.x] = t;
-    }
+    block_sums<true>(match, n, cnt);
 }
 
 // Rows of one compaction block, in probe order, from offs[block] on. The probe
