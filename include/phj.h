@@ -317,10 +317,64 @@ int phj_join_materialize(phj_ctx *ctx, const phj_join_params *p, phj_join_result
  * Synchronous. */
 int phj_join_inner_count(phj_ctx *ctx, const phj_join_params *p, phj_join_result *r);
 int phj_join_inner(phj_ctx *ctx, const phj_join_params *p, phj_join_result *r);
-/* The rows of the last phj_join_materialize / phj_join_inner: device pointer
- * (ctx-owned, valid until the next materialised join) and count. */
+
+/* ---- outer and anti joins: rows for tuples without a partner ----
+ * Replaces nothing in the reference. Rows fall into three classes, and a join
+ * kind is a set of classes: */
+#define PHJ_ROWS_PAIRS      0x1  /* {id, payload_a, payload_b} per (build tuple, probe tuple) pair: phj_join_inner's rows */
+#define PHJ_ROWS_PROBE_ONLY 0x2  /* {id, null_payload, payload_b} per probe tuple with no equal build key */
+#define PHJ_ROWS_BUILD_ONLY 0x4  /* {id, payload_a, null_payload} per build tuple with no equal probe key */
+/*   classes 1: inner              3: probe-preserving outer   5: build-preserving outer
+ *           7: full outer         2: probe anti               4: build anti
+ *           6: both anti sides
+ * classes == 0 or any bit above 0x4 gives PHJ_ERR_INVALID. */
+typedef struct phj_row_counts {
+    uint64_t pairs;       /* always filled: phj_join_inner_count's matches, 64-bit exact */
+    uint64_t probe_only;  /* filled when PHJ_ROWS_PROBE_ONLY is asked, else 0 */
+    uint64_t build_only;  /* filled when PHJ_ROWS_BUILD_ONLY is asked, else 0 */
+    uint64_t rows;        /* the sum of the classes asked for == r->matches */
+} phj_row_counts;
+/* phj_join_rows_count fills r and n and writes no rows (the rows of an earlier
+ * materialised join stay as they are); phj_join_rows also materialises the
+ * rows into the ctx-owned row buffer that phj_joined_rows / phj_joined_download
+ * serve.
+ *  - Row layout. First the probe part: the rows of classes 0x1 and 0x2,
+ *    grouped by probe tuple, the groups in the probe side's storage order
+ *    (input order for NoPartitioning, partition order for the radix join),
+ *    exactly as phj_join_inner orders them. A probe tuple without a partner
+ *    contributes its one null row at its place in that order (class 0x2) or
+ *    nothing. The build_only rows follow the probe part, in unspecified order.
+ *    The order inside a group is unspecified.
+ *  - null_payload is the caller's marker for the missing side; the library
+ *    does not interpret it.
+ *  - Rows are addressed with 32 bits. With n->rows >= 2^32 phj_join_rows
+ *    returns PHJ_ERR_RANGE before any row is written or the row buffer is
+ *    grown; the counts are still filled, and phj_joined_rows then reports 0
+ *    rows.
+ *  - An empty side is not an error: every tuple of the other side is then
+ *    "only", its rows are copied from the bound relation in input order and
+ *    no join runs. Both sides empty gives 0 rows.
+ *  - Single-device contexts only: a group or rank context returns
+ *    PHJ_ERR_STATE ("single-device contexts only").
+ *  - PHJ_ALGO_RADIX and PHJ_ALGO_NO_PARTITIONING; the radix form has
+ *    phj_join_inner's precondition.
+ *  - A later phj_join_materialize or phj_join_inner replaces the rows, and the
+ *    reverse.
+ *  - Timers beside the partition / np.build timers: `rows.count` (the join,
+ *    marking the build tuples it hits when class 0x4 is asked, plus the
+ *    reduction of the per-probe pair counts), `rows.emit` (offsets, pair rows,
+ *    null rows), `rows.build_only` (count and compaction of the unhit build
+ *    tuples). algorithmic_bytes counts what each pass must move (DESIGN.md
+ *    §Outer and anti joins).
+ * Synchronous. */
+int phj_join_rows_count(phj_ctx *ctx, const phj_join_params *p, uint32_t classes,
+                        phj_join_result *r, phj_row_counts *n);
+int phj_join_rows(phj_ctx *ctx, const phj_join_params *p, uint32_t classes, int64_t null_payload,
+                  phj_join_result *r, phj_row_counts *n);
+/* The rows of the last phj_join_materialize / phj_join_inner / phj_join_rows:
+ * device pointer (ctx-owned, valid until the next materialised join) and count. */
 const phj_joined *phj_joined_rows(phj_ctx *ctx, uint64_t *n);
-/* Copy the first n rows of the last phj_join_materialize / phj_join_inner to host memory. */
+/* Copy the first n rows of the last phj_join_materialize / phj_join_inner / phj_join_rows to host memory. */
 int phj_joined_download(phj_ctx *ctx, phj_joined *host, uint64_t n);
 
 /* ---- building blocks (multi-GPU: range-sharded relations, RCCL exchange) ---- */

@@ -14,14 +14,17 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (ALGO_NO_PARTITIONING, ALGO_RADIX, CTX_EXCHANGE, CTX_LOCAL, HASH_MURMUR3, HASH_XXH3,
-                    PATH_CODE_TABLES, PATH_LDS_JOIN, PATH_NO_PARTITIONING, PATH_PARTITIONED, SIDE_BUILD,
-                    SIDE_PROBE, JoinParams, JoinResult, Partitioned, PhjError)
+from ._capi import (ALGO_NO_PARTITIONING, ALGO_RADIX, BUILD_ANTI, BUILD_OUTER, CTX_EXCHANGE, CTX_LOCAL, FULL_OUTER,
+                    HASH_MURMUR3, HASH_XXH3, INNER, NULL_PAYLOAD, PATH_CODE_TABLES, PATH_LDS_JOIN,
+                    PATH_NO_PARTITIONING, PATH_PARTITIONED, PROBE_ANTI, PROBE_OUTER, ROWS_BUILD_ONLY, ROWS_PAIRS,
+                    ROWS_PROBE_ONLY, SIDE_BUILD, SIDE_PROBE, JoinParams, JoinResult, Partitioned, PhjError, RowCounts)
 
 __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_JOIN", "PATH_CODE_TABLES",
            "PATH_PARTITIONED", "PATH_NO_PARTITIONING", "count_contribution", "count_verdict", "comm_unique_id", "CTX_EXCHANGE", "CTX_LOCAL", "radix_params", "nopart_params", "JoinParams", "JoinResult",
            "Partitioned", "PhjError", "ALGO_RADIX", "ALGO_NO_PARTITIONING", "HASH_XXH3",
-           "HASH_MURMUR3", "SIDE_BUILD", "SIDE_PROBE", "DEFAULT_SEED"]
+           "HASH_MURMUR3", "SIDE_BUILD", "SIDE_PROBE", "DEFAULT_SEED", "RowCounts", "ROWS_PAIRS", "ROWS_PROBE_ONLY",
+           "ROWS_BUILD_ONLY", "INNER", "PROBE_OUTER", "BUILD_OUTER", "FULL_OUTER", "PROBE_ANTI", "BUILD_ANTI",
+           "NULL_PAYLOAD"]
 
 DEFAULT_SEED = 0x9E3779B97F4A7C15
 PART_STABLE = 0x1   # include/phj.h PHJ_PART_STABLE
@@ -271,6 +274,26 @@ class Context:
         r = JoinResult()
         self._check(self._L.phj_join_inner(self._h, C.byref(params), C.byref(r)))
         return r
+
+    def join_rows_count(self, params: JoinParams, classes: int):
+        """phj_join_rows_count: (JoinResult, RowCounts) of the join kind
+        `classes` (a set of ROWS_PAIRS / ROWS_PROBE_ONLY / ROWS_BUILD_ONLY, or
+        one of INNER ... BUILD_ANTI); no rows. r.matches == counts.rows."""
+        r, n = JoinResult(), RowCounts()
+        self._check(self._L.phj_join_rows_count(self._h, C.byref(params), classes, C.byref(r), C.byref(n)))
+        return r, n
+
+    def join_rows(self, params: JoinParams, classes: int, null_payload: int = NULL_PAYLOAD):
+        """phj_join_rows: the rows of the join kind `classes`: the probe part
+        (pair rows and, for a probe tuple without a partner, {id, null_payload,
+        payloadB}) grouped by probe tuple, then {id, payloadA, null_payload}
+        per build tuple nobody asked for. Returns (JoinResult, RowCounts);
+        read the rows with joined(). Raises PhjError (PHJ_ERR_RANGE) at 2^32
+        rows or more."""
+        r, n = JoinResult(), RowCounts()
+        self._check(self._L.phj_join_rows(self._h, C.byref(params), classes, null_payload, C.byref(r),
+                                          C.byref(n)))
+        return r, n
 
     def joined(self, n: int | None = None) -> np.ndarray:
         """Rows of the last materialised join as an (n, 3) int64 array

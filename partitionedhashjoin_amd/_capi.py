@@ -40,13 +40,17 @@ EXPORTED = [
     "phj_ctx_create_ex", "phj_ctx_create_device", "phj_comm_unique_id", "phj_ctx_create_rank",
     "phj_ctx_info", "phj_shard_range", "phj_probe_pass1", "phj_debug_poison_chunk_table", "phj_debug_poison_alloc", "phj_debug_fail_member", "phj_debug_exchange_block", "phj_exchange_geometry",
     "phj_exchange_layout", "phj_count_contribution", "phj_count_verdict", "phj_join_path",
-    "phj_join_inner_count", "phj_join_inner",
+    "phj_join_inner_count", "phj_join_inner", "phj_join_rows_count", "phj_join_rows",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
 CTX_LOCAL = 0x2      # ... exchange by device copies; devices may repeat (rehearsal on one GPU)
 UNIQUE_ID_BYTES = 128
 PATH_NO_PARTITIONING, PATH_LDS_JOIN, PATH_CODE_TABLES, PATH_PARTITIONED = 0, 1, 2, 3   # phj_join_path
+# phj_join_rows: the row classes and the join kinds they make
+ROWS_PAIRS, ROWS_PROBE_ONLY, ROWS_BUILD_ONLY = 0x1, 0x2, 0x4
+INNER, PROBE_OUTER, BUILD_OUTER, FULL_OUTER, PROBE_ANTI, BUILD_ANTI = 1, 3, 5, 7, 2, 4
+NULL_PAYLOAD = -2**63   # the default marker for the missing side (INT64_MIN)
 
 
 class Tuple(C.Structure):
@@ -79,6 +83,16 @@ class JoinResult(C.Structure):
                 "exchange_ms": self.exchange_ms,
                 "algorithmic_bytes": self.algorithmic_bytes,
                 "num_partitions": self.num_partitions, "timers": self.timers()}
+
+
+class RowCounts(C.Structure):
+    """phj_row_counts: rows per class of phj_join_rows / phj_join_rows_count."""
+    _fields_ = [("pairs", C.c_uint64), ("probe_only", C.c_uint64), ("build_only", C.c_uint64),
+                ("rows", C.c_uint64)]
+
+    def as_dict(self):
+        return {"pairs": self.pairs, "probe_only": self.probe_only, "build_only": self.build_only,
+                "rows": self.rows}
 
 
 class Partitioned(C.Structure):
@@ -148,6 +162,10 @@ def load():
         "phj_join_materialize": (i, [P, C.POINTER(JoinParams), C.POINTER(JoinResult)]),
         "phj_join_inner_count": (i, [P, C.POINTER(JoinParams), C.POINTER(JoinResult)]),
         "phj_join_inner": (i, [P, C.POINTER(JoinParams), C.POINTER(JoinResult)]),
+        "phj_join_rows_count": (i, [P, C.POINTER(JoinParams), C.c_uint32, C.POINTER(JoinResult),
+                                    C.POINTER(RowCounts)]),
+        "phj_join_rows": (i, [P, C.POINTER(JoinParams), C.c_uint32, i64, C.POINTER(JoinResult),
+                              C.POINTER(RowCounts)]),
         "phj_joined_rows": (P, [P, C.POINTER(u64)]),
         "phj_joined_download": (i, [P, P, u64]),
     }

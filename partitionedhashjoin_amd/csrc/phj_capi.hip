@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <type_traits>
 #include <unordered_map>
@@ -34,6 +35,7 @@
 #include "phj_cluster.h"
 #include "phj_join.h"
 #include "phj_inner.h"
+#include "phj_outer.h"
 #include "phj_mat.h"
 #include "phj_partition.h"
 #include "phj_table.h"
@@ -172,6 +174,7 @@ struct phj_ctx {
     DevBuf np_uni;                     // code-table NoPartitioning: {uniform?, cap} (k_np_ct_plan)
     DevBuf fitems, split, cl_prof;
     DevBuf mat_mark, mat_cnt, mat_rows;   // materialised join: per-probe match, block offsets, rows
+    DevBuf row_hit, row_only, row_cnt;    // phj_join_rows: build hit flags, probe-only bitmap, build block offsets
     uint64_t mat_n = 0;   // fused join: item slots; wave clocks {build, probe} since the last timer reset
     std::vector<hipEvent_t> evpool;
     size_t evnext = 0;
@@ -2244,6 +2247,312 @@ int join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool em
     return PHJ_OK;
 }
 
+// ---- rows by class (phj_outer.h): pairs, probe-only, build-only ----
+
+// What the passes of phj_join_rows must move beyond the inner join's
+// (DESIGN.md §Outer and anti joins). F = bytes of hit flags, one per element
+// of the build storage. Count: the inner count pass; with build-only rows the
+// flags cleared and (at most) every one stored; with probe-only rows pairs[]
+// read and written and the bitmap written. Emit: the offsets (pairs[] read
+// twice, written once); with pair rows the inner emit pass; the bitmap read
+// and, per null row, its offset, its probe tuple and 24 B written. Build-only:
+// the flags read twice (count, write; NoPartitioning: with the table beside
+// them) and, per row, a build tuple read and 24 B written.
+uint64_t rows_count_bytes(uint64_t inner_count, uint64_t F, uint64_t nS, uint32_t classes) {
+    return inner_count + ((classes & PHJ_ROWS_BUILD_ONLY) ? 2 * F : 0) +
+           ((classes & PHJ_ROWS_PROBE_ONLY) ? nS * 8 + nS / 8 : 0);
+}
+uint64_t rows_emit_bytes(uint64_t nS, uint64_t pair_rows, uint64_t probe_only, uint64_t build_bytes) {
+    return nS * 12 + (pair_rows ? build_bytes + nS * (16 + 4) + pair_rows * (8 + 24) : 0) +
+           (probe_only ? nS / 8 + probe_only * (4 + 16 + 24) : 0);
+}
+uint64_t rows_build_only_bytes(uint64_t F, uint64_t table_bytes, uint64_t build_only, bool write) {
+    return F + table_bytes + (write ? build_only * (16 + 24) : 0);
+}
+
+int rows_range_error(phj_ctx* c, uint64_t rows) {
+    return set_err(c, PHJ_ERR_RANGE, "phj_join_rows: " + std::to_string(rows) +
+                                         " rows, rows are addressed with 32 bits (limit 2^32 - 1)");
+}
+
+// What the two algorithms hand to rows_passes: the probe side in storage
+// order (pairs[] has one word per tuple), the build storage the hit flags
+// index, and their join kernel as count pass (bmark: also marking into
+// c->row_hit) and as emit pass.
+struct RowsJob {
+    uint64_t nS = 0;
+    const longlong2* s_aos = nullptr;             // NoPartitioning: AoS tuples
+    const int64_t *sk = nullptr, *sp = nullptr;   // radix: the partitioned columns
+    uint64_t nF = 0;                              // elements of the build storage
+    const NPBucket* tab = nullptr;                // NoPartitioning: the table (keys), rp = np_pays
+    const int64_t *rk = nullptr, *rp = nullptr;
+    uint64_t count_bytes = 0, build_bytes = 0, table_bytes = 0;
+    std::function<int(bool)> count;
+    std::function<int(JoinedRow*, uint32_t)> emit;
+};
+
+// Everything behind the partitioning / table build: the count pass (with hit
+// marking) and the reductions, the counts read back, then (emit) the 2^32
+// rule, offsets, pair rows, null rows and the unhit build tuples. One stream,
+// one synchronisation at the end; *end: the event behind the last kernel.
+int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, const RowsJob& J, phj_join_result* r,
+                phj_row_counts* n, hipEvent_t* end) {
+    const bool want_p = classes & PHJ_ROWS_PAIRS, want_s = classes & PHJ_ROWS_PROBE_ONLY,
+               want_b = classes & PHJ_ROWS_BUILD_ONLY;
+    const bool np = J.tab != nullptr;
+    const uint32_t nblk = static_cast<uint32_t>((J.nS + kMatBlock - 1) / kMatBlock);
+    const uint32_t fblk = static_cast<uint32_t>((J.nF + kMatBlock - 1) / kMatBlock);
+    if (want_s) PHJ_TRY(ensure(c, c->row_only, (J.nS + 63) / 64 * 8));
+    if (want_b) {
+        PHJ_TRY(ensure(c, c->row_hit, J.nF));
+        PHJ_TRY(ensure(c, c->row_cnt, (static_cast<size_t>(fblk) + 1) * 4));
+    }
+    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
+    auto* cnt = static_cast<unsigned long long*>(c->count.p);   // {pairs, probe_only, build_only}
+    auto* only = static_cast<uint64_t*>(c->row_only.p);
+    auto* hit = static_cast<uint8_t*>(c->row_hit.p);
+    auto* bcnt = static_cast<uint32_t*>(c->row_cnt.p);
+    PHJ_HIP(c, hipMemsetAsync(cnt + 1, 0, 16, c->ks));
+    uint64_t bytes = rows_count_bytes(J.count_bytes, J.nF, J.nS, classes);
+    r->algorithmic_bytes += bytes;
+    PHJ_TRY(timer_begin(c, "rows.count", bytes));
+    if (want_b) PHJ_HIP(c, hipMemsetAsync(hit, 0, J.nF, c->ks));   // on every call: never the allocation's contents
+    PHJ_TRY(J.count(want_b));
+    if (want_s) {
+        if (want_p) hipLaunchKernelGGL(k_rows_map<true>, dim3(nblk), dim3(kBlock), 0, c->ks, pairs, J.nS, only, cnt + 1);
+        else hipLaunchKernelGGL(k_rows_map<false>, dim3(nblk), dim3(kBlock), 0, c->ks, pairs, J.nS, only, cnt + 1);
+        PHJ_LAUNCHED(c, "k_rows_map");
+    }
+    PHJ_TRY(timer_end(c));
+    if (want_b) {
+        bytes = rows_build_only_bytes(J.nF, J.table_bytes, 0, false);
+        r->algorithmic_bytes += bytes;
+        PHJ_TRY(timer_begin(c, "rows.build_only", bytes));
+        PHJ_HIP(c, hipMemsetAsync(bcnt, 0, (static_cast<size_t>(fblk) + 1) * 4, c->ks));
+        if (np) hipLaunchKernelGGL(k_build_only_count<true>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, bcnt, cnt + 2);
+        else hipLaunchKernelGGL(k_build_only_count<false>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, bcnt, cnt + 2);
+        PHJ_LAUNCHED(c, "k_build_only_count");
+        PHJ_TRY(timer_end(c));
+    }
+    PHJ_TRY(mark(c, end));
+    unsigned long long h[3] = {0, 0, 0};
+    PHJ_HIP(c, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->ks));
+    PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    PHJ_TRY(check_chunk_errors(c));
+    n->pairs = h[0];
+    n->probe_only = want_s ? h[1] : 0;
+    n->build_only = want_b ? h[2] : 0;
+    const uint64_t pair_rows = want_p ? n->pairs : 0;
+    const uint64_t probe_rows = pair_rows + n->probe_only;
+    n->rows = probe_rows + n->build_only;
+    r->matches = n->rows;
+    if (!emit) return PHJ_OK;
+    // nothing is written and the row buffer is not grown above the limit
+    // (below it no block sum of the offsets can have wrapped either)
+    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows);
+    PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
+    PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, n->rows) * sizeof(JoinedRow)));
+    auto* rows = static_cast<JoinedRow*>(c->mat_rows.p);
+    if (probe_rows > 0) {
+        bytes = rows_emit_bytes(J.nS, pair_rows, n->probe_only, J.build_bytes);
+        r->algorithmic_bytes += bytes;
+        PHJ_TRY(timer_begin(c, "rows.emit", bytes));
+        PHJ_TRY(inner_offsets(c, J.nS));
+        if (pair_rows > 0) PHJ_TRY(J.emit(rows, static_cast<uint32_t>(probe_rows)));
+        if (n->probe_only > 0) {
+            const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((J.nS + kBlock - 1) / kBlock, 8192));
+            hipLaunchKernelGGL(k_rows_fill, dim3(grid), dim3(kBlock), 0, c->ks, only, pairs, J.nS, J.s_aos, J.sk, J.sp,
+                               null_payload, rows, static_cast<uint32_t>(probe_rows));
+            PHJ_LAUNCHED(c, "k_rows_fill");
+        }
+        PHJ_TRY(timer_end(c));
+    }
+    if (n->build_only > 0) {
+        bytes = rows_build_only_bytes(J.nF, J.table_bytes, n->build_only, true);
+        r->algorithmic_bytes += bytes;
+        PHJ_TRY(timer_begin(c, "rows.build_only", bytes));
+        PHJ_TRY(scan_u32(c, bcnt, fblk + 1, 1, fblk + 1));
+        const uint32_t row0 = static_cast<uint32_t>(probe_rows), nrows = static_cast<uint32_t>(n->rows);
+        if (np) hipLaunchKernelGGL(k_build_only_write<true>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, rows, row0, nrows);
+        else hipLaunchKernelGGL(k_build_only_write<false>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, rows, row0, nrows);
+        PHJ_LAUNCHED(c, "k_build_only_write");
+        PHJ_TRY(timer_end(c));
+    }
+    PHJ_TRY(mark(c, end));
+    PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    return PHJ_OK;
+}
+
+int join_nopart_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, bool emit,
+                     phj_join_result* r, phj_row_counts* n) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
+        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
+    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (S.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    NPHome g{};
+    hipEvent_t e0 = nullptr, e1, e2;
+    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));
+    PHJ_TRY(ensure(c, c->count, 32));
+    PHJ_TRY(np_build(c, p, true, g, &e0));
+    PHJ_TRY(mark(c, &e1));
+    PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
+    const auto* S_rel = reinterpret_cast<const longlong2*>(S.rel);
+    const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
+    const auto* pays = static_cast<const int64_t*>(c->np_pays.p);
+    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
+    auto* cnt = static_cast<unsigned long long*>(c->count.p);
+    RowsJob J;
+    J.nS = S.n;
+    J.s_aos = S_rel;
+    J.nF = static_cast<uint64_t>(g.nb) * kNPSlots;
+    J.tab = tab;
+    J.rp = pays;
+    J.table_bytes = J.build_bytes = static_cast<uint64_t>(g.nb) * 64;
+    J.count_bytes = inner_count_bytes(0, S.n) + J.table_bytes;
+    J.count = [&](bool bmark) -> int {
+        with_hash(p->hash, [&](auto h) {
+            constexpr int HK = decltype(h)::value;
+            // (marking: the flags travel in the count pass's unused row pointer, phj_inner.h)
+            if (bmark)
+                hipLaunchKernelGGL((k_np_inner<HK, false, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
+                                   g, p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(c->row_hit.p), 0u);
+            else
+                hipLaunchKernelGGL((k_np_inner<HK, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
+                                   p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
+        });
+        PHJ_LAUNCHED(c, "k_np_inner");
+        return PHJ_OK;
+    };
+    J.emit = [&](JoinedRow* rows, uint32_t nrows) -> int {
+        with_hash(p->hash, [&](auto h) {
+            hipLaunchKernelGGL((k_np_inner<decltype(h)::value, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
+                               pays, g, p->hash_seed, pairs, cnt, rows, nrows);
+        });
+        PHJ_LAUNCHED(c, "k_np_inner");
+        return PHJ_OK;
+    };
+    r->algorithmic_bytes = R.n * 32 + J.table_bytes;
+    PHJ_TRY(rows_passes(c, classes, null_payload, emit, J, r, n, &e2));
+    r->partition_ms = 0;
+    r->build_ms = elapsed(c, e0, e1);
+    r->probe_ms = elapsed(c, e1, e2);
+    r->total_ms = elapsed(c, e0, e2);
+    r->num_partitions = 0;
+    return fill_timers(c, r);
+}
+
+int join_radix_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, bool emit,
+                    phj_join_result* r, phj_row_counts* n) {
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    const SideState& S = c->side[PHJ_SIDE_PROBE];
+    if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    FusedJoin j;
+    PHJ_TRY(fused_setup(c, p, "radix row join", j));
+    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
+    RowsJob J;
+    J.nS = j.nS;
+    J.sk = S.view.keys;
+    J.sp = S.view.payloads;
+    J.nF = R.view.n;
+    J.rk = R.view.keys;
+    J.rp = R.view.payloads;
+    J.build_bytes = R.n * 8;
+    J.count_bytes = inner_count_bytes(R.n, j.nS);
+    J.count = [&](bool bmark) -> int {
+        hipLaunchKernelGGL(k_fused_items, dim3((j.fa.L.P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, j.fa.sbounds,
+                           j.fa.L.P, static_cast<FusedItem*>(c->fitems.p));
+        PHJ_LAUNCHED(c, "k_fused_items");
+        with_hash(j.pl.hk, [&](auto h) {
+            constexpr int HK = decltype(h)::value;
+            if (bmark)
+                hipLaunchKernelGGL((k_inner_fused<HK, false, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, pairs,
+                                   S.view.payloads, static_cast<JoinedRow*>(c->row_hit.p), 0u);
+            else
+                hipLaunchKernelGGL((k_inner_fused<HK, false>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, pairs,
+                                   S.view.payloads, static_cast<JoinedRow*>(nullptr), 0u);
+        });
+        PHJ_LAUNCHED(c, "k_inner_fused");
+        return PHJ_OK;
+    };
+    J.emit = [&](JoinedRow* rows, uint32_t nrows) -> int {
+        with_hash(j.pl.hk, [&](auto h) {
+            hipLaunchKernelGGL((k_inner_fused<decltype(h)::value, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, pairs,
+                               S.view.payloads, rows, nrows);
+        });
+        PHJ_LAUNCHED(c, "k_inner_fused");
+        return PHJ_OK;
+    };
+    r->num_partitions = j.requested;
+    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n);
+    hipEvent_t p1;
+    PHJ_TRY(rows_passes(c, classes, null_payload, emit, J, r, n, &p1));
+    return fused_times(c, j, p1, r);
+}
+
+// An empty side: nothing to join; every tuple of the other side is "only".
+int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, phj_join_result* r,
+                    phj_row_counts* n) {
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    const SideState& S = c->side[PHJ_SIDE_PROBE];
+    n->probe_only = (classes & PHJ_ROWS_PROBE_ONLY) ? S.n : 0;   // (at least one of the two is empty)
+    n->build_only = (classes & PHJ_ROWS_BUILD_ONLY) ? R.n : 0;
+    n->rows = n->probe_only + n->build_only;
+    r->matches = n->rows;
+    if (!emit || n->rows == 0) return PHJ_OK;
+    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows);
+    PHJ_TRY(ensure(c, c->mat_rows, n->rows * sizeof(JoinedRow)));
+    const bool build = n->build_only > 0;
+    const SideState& T = build ? R : S;
+    hipEvent_t e0, e1;
+    PHJ_TRY(mark(c, &e0));
+    PHJ_TRY(timer_begin(c, build ? "rows.build_only" : "rows.emit", n->rows * (16 + 24)));
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((T.n + kBlock - 1) / kBlock, 8192));
+    hipLaunchKernelGGL(k_rows_side, dim3(grid), dim3(kBlock), 0, c->ks, reinterpret_cast<const longlong2*>(T.rel), T.n,
+                       null_payload, build, static_cast<JoinedRow*>(c->mat_rows.p));
+    PHJ_LAUNCHED(c, "k_rows_side");
+    PHJ_TRY(timer_end(c));
+    PHJ_TRY(mark(c, &e1));
+    PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    r->algorithmic_bytes = n->rows * (16 + 24);
+    r->probe_ms = r->total_ms = elapsed(c, e0, e1);
+    return fill_timers(c, r);
+}
+
+// phj_join_rows_count (emit = false) / phj_join_rows.
+int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, phj_join_result* r,
+              phj_row_counts* n, bool emit, const char* what) {
+    if (!c || !r || !n) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    (void)hipGetLastError();
+    if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
+    constexpr uint32_t all = PHJ_ROWS_PAIRS | PHJ_ROWS_PROBE_ONLY | PHJ_ROWS_BUILD_ONLY;
+    if (classes == 0 || (classes & ~all))
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": classes must be a non-empty set of PHJ_ROWS_*");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    std::memset(r, 0, sizeof(*r));
+    std::memset(n, 0, sizeof(*n));
+    c->defer_timers = false;
+    c->lean_timers = false;
+    c->timer_skipped = false;
+    c->count_pinned = false;
+    reset_timers(c);
+    if (emit) c->mat_n = 0;
+    if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
+        return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    // decided here: np_build refuses an empty build side, and no table or
+    // partition is needed to know that the other side has no partner
+    if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0)
+        PHJ_TRY(rows_empty_side(c, classes, null_payload, emit, r, n));
+    else if (p->algo == PHJ_ALGO_NO_PARTITIONING) PHJ_TRY(join_nopart_rows(c, p, classes, null_payload, emit, r, n));
+    else PHJ_TRY(join_radix_rows(c, p, classes, null_payload, emit, r, n));
+    if (emit) c->mat_n = n->rows;
+    return PHJ_OK;
+}
+
 int ctx_create_device(int device, phj_ctx** out) {
     if (!out) return PHJ_ERR_INVALID;
     *out = nullptr;
@@ -2437,7 +2746,7 @@ void phj_ctx_destroy(phj_ctx* c) {
             free_buf(*b);
     }
     for (DevBuf* b : {&c->ht_tab, &c->ht_desc, &c->r_codes, &c->r_bounds, &c->scan_partials, &c->prep, &c->tkeys, &c->tpays, &c->toffs, &c->gcursor, &c->items, &c->biglist,
-                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->cl_done})
+                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->cl_done})
         free_buf(*b);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -3038,6 +3347,16 @@ int phj_join_inner_count(phj_ctx* c, const phj_join_params* p, phj_join_result* 
 
 int phj_join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     return join_inner(c, p, r, true, "phj_join_inner");
+}
+
+int phj_join_rows_count(phj_ctx* c, const phj_join_params* p, uint32_t classes, phj_join_result* r,
+                        phj_row_counts* n) {
+    return join_rows(c, p, classes, 0, r, n, false, "phj_join_rows_count");
+}
+
+int phj_join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, phj_join_result* r,
+                  phj_row_counts* n) {
+    return join_rows(c, p, classes, null_payload, r, n, true, "phj_join_rows");
 }
 
 const phj_joined* phj_joined_rows(phj_ctx* c, uint64_t* n) {

@@ -29,13 +29,25 @@ namespace phj {
 
 constexpr uint32_t kInnerWide = 64;   // k_inner_fused: bucket length from which the wave shares a probe key's compares
 constexpr uint32_t kInnerWideLanes = 16;   // ... count pass: only while at most this many lanes have such a bucket
+constexpr uint32_t kInnerHitBit = 0x80000000u;   // k_inner_fused, BMARK: lr[pos] = in-round index | this once compared equal
+
+// BMARK (the count pass of phj_join_rows with build-only rows, phj_outer.h):
+// the join also says which build tuples met an equal probe key, one byte per
+// build tuple, cleared by the host before the launch. A flag is only ever
+// stored as 1 (several waves serve one partition, thousands of probe tuples
+// one hot key), so no atomic and no order between the writers is needed.
+// The count pass stores no rows: its `out` argument carries the flags, so the
+// kernels' arguments, and with them the code of the instantiations
+// phj_join_inner uses, stay as they were.
 
 // The slots of one NoPartitioning bucket (its four 16-B words in q) equal to
-// key; EMIT: their rows from out[row] on. Returns how many.
-template <bool EMIT>
+// key; EMIT: their rows from out[row] on; BMARK: hit[b * kNPSlots + s] = 1 for
+// each (tested first: a hot key's run is walked by thousands of probe tuples,
+// whose steady state is then cached reads). Returns how many.
+template <bool EMIT, bool BMARK>
 __device__ __forceinline__ uint32_t np_bucket_pairs(const longlong2 (&q)[4], uint32_t b, int64_t key,
                                                     const int64_t* pays, int64_t pb, JoinedRow* out, uint32_t row,
-                                                    uint32_t nrows) {
+                                                    uint32_t nrows, uint8_t* hit) {
     int64_t ks[kNPSlots];
     const uint32_t fill = np_unpack(q, ks);
     const uint32_t c = fill < kNPSlots ? fill : kNPSlots;
@@ -49,6 +61,10 @@ __device__ __forceinline__ uint32_t np_bucket_pairs(const longlong2 (&q)[4], uin
                 r.payload_a = pays[static_cast<size_t>(b) * kNPSlots + s];
                 r.payload_b = pb;
                 out[row + n] = r;
+            }
+            if (BMARK) {
+                uint8_t* f = hit + static_cast<size_t>(b) * kNPSlots + s;
+                if (*f == 0) *f = 1;
             }
             n++;
         }
@@ -64,12 +80,16 @@ __device__ __forceinline__ uint32_t np_bucket_pairs(const longlong2 (&q)[4], uin
 // EMIT = false: pairs[i] = that number, *count += their sum.
 // EMIT = true:  pairs[i] is probe tuple i's first row; rows beyond nrows are
 //               not stored (the count pass saw the same table: there are none).
-template <int HK, bool EMIT>
+// BMARK (EMIT = false only): out holds the hit flags of the table's slots,
+//               indexed like pays (b * kNPSlots + s).
+template <int HK, bool EMIT, bool BMARK = false>
 __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_t nS, const NPBucket* tab,
                                                      const int64_t* pays, NPHome g, uint64_t seed, uint32_t* pairs,
                                                      unsigned long long* count, JoinedRow* out, uint32_t nrows) {
+    static_assert(!(EMIT && BMARK), "hit flags are written by the count pass");
     __shared__ unsigned long long red[kWaves];
     constexpr int IT = 4;   // as k_np_probe: every home bucket of a round requested before any compare
+    uint8_t* hit = BMARK ? reinterpret_cast<uint8_t*>(out) : nullptr;
     unsigned long long total = 0;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock * IT;
     for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kBlock * IT; base < nS; base += stride) {
@@ -83,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_
             if (i >= nS) continue;
             const int64_t key = t[j].x;
             const uint32_t row = EMIT ? pairs[i] : 0u;
-            uint32_t n = np_bucket_pairs<EMIT>(q[j], b[j], key, pays, t[j].y, out, row, nrows);
+            uint32_t n = np_bucket_pairs<EMIT, BMARK>(q[j], b[j], key, pays, t[j].y, out, row, nrows, hit);
             bool full = static_cast<uint32_t>(q[j][3].y) >= kNPSlots;
             uint32_t bb = b[j];
             for (uint32_t step = 1; full && step < g.nb; step++) {   // full bucket: the run goes on
@@ -92,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_
                 longlong2 w[4];
 #pragma unroll
                 for (int x = 0; x < 4; x++) w[x] = bp[x];
-                n += np_bucket_pairs<EMIT>(w, bb, key, pays, t[j].y, out, row + n, nrows);
+                n += np_bucket_pairs<EMIT, BMARK>(w, bb, key, pays, t[j].y, out, row + n, nrows, hit);
                 full = static_cast<uint32_t>(w[3].y) >= kNPSlots;
             }
             if (!EMIT) {
@@ -126,11 +146,18 @@ __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_
 //               partition is empty), *a.count += their sum.
 // EMIT = true:  pairs[s] is probe tuple s's first row on entry and the cursor
 //               behind its rows written so far between rounds.
-template <int HK, bool EMIT>
+// BMARK (EMIT = false only): out holds the hit flags of the partitioned build
+//               relation's rows. lr[] is free in the count pass, so it keeps
+//               each table position's in-round index and, once a probe key
+//               compared equal there (either compare path), kInnerHitBit;
+//               after the round's probe loop each lane turns its RPL
+//               positions' bits into the flags of build rows rlo + r0 + index.
+template <int HK, bool EMIT, bool BMARK = false>
 __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* pairs, const int64_t* spays,
                                                         JoinedRow* out, uint32_t nrows) {
     constexpr int TCAP = 256, RPL = TCAP / 64, OCAP = TCAP / 2 + 1, KPL = 4;
     constexpr uint32_t SUB = 64 * KPL;
+    static_assert(!(EMIT && BMARK), "hit flags are written by the count pass");
     __shared__ int64_t lk_all[kWaves][TCAP];
     __shared__ uint32_t lr_all[kWaves][TCAP];
     __shared__ uint32_t lo_all[kWaves][OCAP];
@@ -141,6 +168,7 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
     uint32_t* lr = lr_all[wave];
     uint32_t* loffs = lo_all[wave];
     uint32_t* lcur = cur_all[wave];
+    uint8_t* hitf = BMARK ? reinterpret_cast<uint8_t*>(out) : nullptr;
     const int64_t* rkeys = a.L.seg[0].keys;
     const int64_t* rpays = a.L.seg[0].pays;
     const uint32_t* rb = a.L.seg[0].bounds;
@@ -198,6 +226,7 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
                     const uint32_t pos = atomicAdd(&lcur[bk[j]], 1u);
                     lk[pos] = rk[j];
                     if (EMIT) lr[pos] = rlo + r0 + f;
+                    if (BMARK) lr[pos] = f;
                 }
             }
             wave_lds_sync();
@@ -241,6 +270,10 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
                                         out[row + n] = r;
                                     }
                                 }
+                                if (BMARK) {   // (lanes on one hot key store the same word)
+                                    const uint32_t v = lr[t];
+                                    if (!(v & kInnerHitBit)) lr[t] = v | kInnerHitBit;
+                                }
                                 n++;
                             }
                         }
@@ -267,6 +300,10 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
                                     out[at] = r;
                                 }
                             }
+                            if (BMARK && hit) {
+                                const uint32_t v = lr[t];
+                                if (!(v & kInnerHitBit)) lr[t] = v | kInnerHitBit;
+                            }
                             wn += __popcll(bal);
                         }
                         if (lane == static_cast<uint32_t>(src)) n = wn;
@@ -280,6 +317,15 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
                             total += n;
                         }
                     }
+                }
+            }
+            if (BMARK) {
+                wave_lds_sync();   // every lane's hit bits before they are read
+#pragma unroll
+                for (int j = 0; j < RPL; j++) {
+                    const uint32_t pos = j * 64 + lane;
+                    const uint32_t v = pos < mr ? lr[pos] : 0u;
+                    if (v & kInnerHitBit) hitf[rlo + r0 + (v & ~kInnerHitBit)] = 1;
                 }
             }
             wave_lds_sync();   // this round's LDS reads before the next round's stores

@@ -72,7 +72,9 @@ struct GpuConfiguration {
     double TableRatio = 0.0;         // NoPartitioning slots per tuple (0: default)
     bool Materialize = false;        // --materialize on: Run() returns the joined rows (phj_join_materialize)
     bool MaterializeAll = false;     // --materialize all: Run() returns every (build, probe) pair (phj_join_inner)
-    std::vector<int> Devices;        // --gpus N / --devices a,b,..: the context's devices (empty: {Device})
+    uint32_t RowClasses = 0;         // --join-kind: Run() returns that kind's rows (phj_join_rows; PHJ_ROWS_* set, 0 = off)
+    int64_t NullPayload = INT64_MIN; // ... the payload standing for the missing side of an outer / anti row
+    std::vector<int> Devices;       // --gpus N / --devices a,b,..: the context's devices (empty: {Device})
     uint32_t ContextFlags = 0;       // --exchange rccl|local: PHJ_CTX_EXCHANGE / PHJ_CTX_LOCAL
 };
 

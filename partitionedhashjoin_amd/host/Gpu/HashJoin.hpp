@@ -13,8 +13,12 @@
 // GpuConfiguration::Materialize asks for the rows (phj_join_materialize:
 // one JoinedTuple per matching probe tuple, copied back) or
 // GpuConfiguration::MaterializeAll for the inner join's (phj_join_inner: one
-// per pair of a build and a probe tuple with equal ids); the matched
-// count (MaterializeAll: the pair count) is logged ("Joined N tuples", RadixCluster/HashJoin.hpp:320-321),
+// per pair of a build and a probe tuple with equal ids) or
+// GpuConfiguration::RowClasses for an outer / anti join kind's (phj_join_rows:
+// pair rows, and rows with NullPayload on the missing side for the probe and
+// build tuples without a partner; the counts per class are added to the
+// results as `pairs`, `probe_only`, `build_only`); the matched
+// count (MaterializeAll: the pair count, RowClasses: the row count) is logged ("Joined N tuples", RadixCluster/HashJoin.hpp:320-321),
 // added to the results as `matches`, and kept in GetNumberOfJoinedTuples().
 // C ABI errors surface as std::runtime_error / std::invalid_argument, which the
 // CLI catches and turns into exit(1) (src/main.cpp:277-281).
@@ -83,10 +87,22 @@ inline std::chrono::nanoseconds ms_to_ns(double ms) {
 
 // phj_join or, with rows requested, phj_join_materialize (one row per matching
 // probe tuple) / phj_join_inner (all: one row per pair) + the rows copied into
-// the returned table
+// the returned table; with gpu.RowClasses, phj_join_rows of that kind
 inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, const phj_join_params& p,
-                                                                phj_join_result& r, bool materialize,
-                                                                bool all = false) {
+                                                                phj_join_result& r,
+                                                                const Common::GpuConfiguration& gpu,
+                                                                Common::IHashJoinTimer& timer) {
+    const bool materialize = gpu.Materialize, all = gpu.MaterializeAll;
+    if (gpu.RowClasses != 0) {
+        phj_row_counts n{};
+        dev.Check(phj_join_rows(dev.Get(), &p, gpu.RowClasses, gpu.NullPayload, &r, &n));
+        auto out = std::make_shared<Common::Table<Common::JoinedTuple>>(n.rows, Common::generate_uuid());
+        dev.Check(phj_joined_download(dev.Get(), reinterpret_cast<phj_joined*>(out->Data()), n.rows));
+        timer.AddResult("pairs", std::to_string(n.pairs));
+        timer.AddResult("probe_only", std::to_string(n.probe_only));
+        timer.AddResult("build_only", std::to_string(n.build_only));
+        return out;
+    }
     if (!materialize && !all) {
         dev.Check(phj_join(dev.Get(), &p, &r));
         return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());
@@ -157,7 +173,7 @@ class HashJoiner {
         // workspace allocation stays outside the timed phases, as the reference's
         // partitioned-table allocation does (RadixCluster/HashJoin.hpp:195-198)
         m_device->Check(phj_prepare(m_device->Get(), &p));
-        auto joined = internal::join(*m_device, p, r, m_gpu.Materialize, m_gpu.MaterializeAll);
+        auto joined = internal::join(*m_device, p, r, m_gpu, *timer);
         // partition: wall of both partition pipelines; build / probe: device phases
         timer->SetPartitionPhaseDuration(internal::ms_to_ns(r.partition_ms));
         timer->SetBuildPhaseDuration(internal::ms_to_ns(r.build_ms));
@@ -224,7 +240,7 @@ class HashJoiner {
         // workspace allocation stays outside the timed phases, as the reference's
         // partitioned-table allocation does (RadixCluster/HashJoin.hpp:195-198)
         m_device->Check(phj_prepare(m_device->Get(), &p));
-        auto joined = internal::join(*m_device, p, r, m_gpu.Materialize, m_gpu.MaterializeAll);
+        auto joined = internal::join(*m_device, p, r, m_gpu, *timer);
         timer->SetBuildPhaseDuration(internal::ms_to_ns(r.build_ms));
         // the reference's probe figure runs from the build start (Results.hpp:202)
         timer->SetProbePhaseDuration(internal::ms_to_ns(r.build_ms + r.probe_ms));

@@ -16,6 +16,7 @@
 //   --table-ratio X       no-partitioning: table slots per build tuple
 //   --gpus N | --devices a,b,..  several devices (multi-GPU join over RCCL)
 //   --exchange rccl|local  force the multi-GPU path (RCCL world of one / device copies)
+//   --join-kind K         inner|probe-outer|build-outer|full-outer|probe-anti|build-anti: return that kind's rows
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -65,13 +66,16 @@ const char* kHelp =
     "  --table-ratio arg                   No-partitioning table slots per build tuple.\n"
     "  --materialize arg (=off)            on | off | all: return the joined rows (Table<JoinedTuple>);\n"
     "                                      on: one per matching probe tuple, all: one per pair (inner join).\n"
+    "  --join-kind arg                     inner | probe-outer | build-outer | full-outer | probe-anti | build-anti:\n"
+    "                                      return that join's rows; a tuple without a partner gets INT64_MIN\n"
+    "                                      as the missing side's payload.\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
     "  --exchange arg                      rccl | local: force the multi-GPU path (rccl on one device is\n"
     "                                      an RCCL world of one; local = device copies, devices may repeat).\n";
 
-// --materialize on | all: the rows Run() returned (count, and a checksum of their
+// --materialize on | all, --join-kind: the rows Run() returned (count, and a checksum of their
 // columns so a caller can compare runs without the rows themselves)
 void report_rows(const Common::Table<Common::JoinedTuple>& rows, Common::IHashJoinTimer& timer, bool materialize) {
     if (!materialize) return;
@@ -99,7 +103,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
     static const std::set<std::string> known = {"help", "primary", "secondary", "skew", "log", "join", "format",
                                                 "unit", "output", "filename", "partitions", "device", "gpus", "devices", "exchange", "hash",
                                                 "radix-bits", "seed", "hash-seed", "generate", "table-ratio",
-                                                "materialize"};
+                                                "materialize", "join-kind"};
     Common::Configuration c{};
     c.OutputFormatConfig.TimeUnit = "ms";
     c.OutputConfig.File.Name = "hashjoin.txt";
@@ -151,6 +155,19 @@ Common::Configuration parseArguments(int argc, char** argv) {
             else if (vm["materialize"] == "all") c.GpuConfig.MaterializeAll = true;
             else if (vm["materialize"] != "off")
                 throw std::invalid_argument("the argument ('" + vm["materialize"] + "') for option '--materialize' is invalid");
+        }
+        if (vm.count("join-kind")) {
+            static const std::map<std::string, uint32_t> kinds = {
+                {"inner", PHJ_ROWS_PAIRS},
+                {"probe-outer", PHJ_ROWS_PAIRS | PHJ_ROWS_PROBE_ONLY},
+                {"build-outer", PHJ_ROWS_PAIRS | PHJ_ROWS_BUILD_ONLY},
+                {"full-outer", PHJ_ROWS_PAIRS | PHJ_ROWS_PROBE_ONLY | PHJ_ROWS_BUILD_ONLY},
+                {"probe-anti", PHJ_ROWS_PROBE_ONLY},
+                {"build-anti", PHJ_ROWS_BUILD_ONLY}};
+            const auto k = kinds.find(vm["join-kind"]);
+            if (k == kinds.end())
+                throw std::invalid_argument("the argument ('" + vm["join-kind"] + "') for option '--join-kind' is invalid");
+            c.GpuConfig.RowClasses = k->second;
         }
         c.GpuConfig.Hash = PHJ_HASH_XXH3;
         if (vm.count("hash")) {
@@ -206,6 +223,10 @@ Common::Configuration parseArguments(int argc, char** argv) {
         if ((c.GpuConfig.Materialize || c.GpuConfig.MaterializeAll) &&
             (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--materialize on / all runs on one device");
+        if (c.GpuConfig.RowClasses && (c.GpuConfig.Materialize || c.GpuConfig.MaterializeAll))
+            throw std::invalid_argument("--join-kind returns its own rows: not together with --materialize on / all");
+        if (c.GpuConfig.RowClasses && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
+            throw std::invalid_argument("--join-kind runs on one device");
         // validateParsedConfiguration (src/Arguments.hpp:7-18)
         c.OutputConfig.Validate();
         c.OutputFormatConfig.Validate();
@@ -296,7 +317,8 @@ int main(int argc, char** argv) {
                     Gpu::NoPartitioning::HashJoiner<decltype(factory)> joiner(configuration.NoPartitioningConfig, device,
                                                                              factory, configuration.GpuConfig);
                     auto joined = tableA ? joiner.Run(tableA, tableB, timer) : joiner.RunResident(timer);
-                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize || configuration.GpuConfig.MaterializeAll);
+                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize || configuration.GpuConfig.MaterializeAll ||
+                                                     configuration.GpuConfig.RowClasses != 0);
                 };
                 if (configuration.GpuConfig.Hash == PHJ_HASH_MURMUR3) run(Common::Murmur3Hasher(hashSeed));
                 else run(Common::XXHasher(hashSeed));
@@ -324,7 +346,8 @@ int main(int argc, char** argv) {
                     Gpu::RadixClustering::HashJoiner<decltype(factory), H> joiner(
                         configuration.RadixClusteringConfig, device, hasher, factory, configuration.GpuConfig);
                     auto joined = tableA ? joiner.Run(tableA, tableB, timer) : joiner.RunResident(timer);
-                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize || configuration.GpuConfig.MaterializeAll);
+                    report_rows(*joined, *timer, configuration.GpuConfig.Materialize || configuration.GpuConfig.MaterializeAll ||
+                                                     configuration.GpuConfig.RowClasses != 0);
                 };
                 if (configuration.GpuConfig.Hash == PHJ_HASH_MURMUR3) run(Common::Murmur3Hasher(hashSeed));
                 else run(Common::XXHasher(hashSeed));
