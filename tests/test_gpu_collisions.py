@@ -1,0 +1,325 @@
+"""The row joins (phj_join_materialize, phj_join_inner[_count],
+phj_join_rows[_count]) on crafted hash collisions and at their tables' edges.
+
+tests/hashinv.py inverts both hashes, so the keys here are chosen by their
+codes: a crowd of distinct keys in one partition and one LDS bucket (the
+wave-cooperative compare of k_inner_fused with sparse ballots, on both sides
+of the count pass's kInnerWideLanes switch), keys homed in the last bucket of
+the NoPartitioning table or of its region 0 (the overflow list, the wrap to
+bucket 0, the hit flag b * 7 + s of an overflowed tuple), a table without a
+free slot, and the same joins over the chunked pass 1 (chunk_ctx).
+
+The expectation is the numpy restatement of test_gpu_outer (Expect) and the
+oracle's semi-join count, never the library. Payloads are unique on both
+sides, so equal multisets of rows prove which build tuple stands in each row.
+Every property a case relies on is asserted in Python when the case is made,
+before the GPU is touched."""
+import functools
+
+import numpy as np
+import pytest
+
+import partitionedhashjoin_amd as phj
+from hashinv import lds_bucket, np_edge_keys, np_geometry, np_home, partition_mates, partition_of
+from oracle import oracle as O
+from test_gpu_inner import R_BASE, S_BASE, canon, check_dup_case, with_payloads
+from test_gpu_materialize import PARAMS, check_rows
+from test_gpu_outer import NULL, Expect, check, rounds_case
+
+pytestmark = pytest.mark.gpu
+
+BY_NAME = {p[0]: p for p in PARAMS}
+RADIX = [p[0] for p in PARAMS if p[0].startswith("radix")]
+NP = [p[0] for p in PARAMS if p[0].startswith("np")]
+CHUNKED = ["radix-8+8", "radix-4"]
+CLASSES = (7, 4, 2)
+
+TCAP = 256        # csrc/phj_inner.h k_inner_fused: build keys per LDS round
+WIDE = 64         # ... kInnerWide: bucket length compared by the whole wave
+WIDE_LANES = 16   # ... kInnerWideLanes: the count pass goes wide up to this many such lanes of 64
+MATE_BASE = (93 << 32) | 0x3039   # the mates' code below 2^50: LDS bucket 93 of 128, partition 0x3039 & (P - 1)
+
+
+def codes(params, keys):
+    return O.hash_keys(params.hash, np.asarray(keys, dtype=np.int64), params.hash_seed)
+
+
+def filler(rng, bound, n, avoid, distinct=False):
+    """n keys from +-bound, none of them in avoid."""
+    pool = np.setdiff1d(np.arange(-bound, bound, dtype=np.int64), avoid)
+    return rng.choice(pool, n, replace=not distinct)
+
+
+def requested_partitions(params):
+    return params.num_partitions or 1 << (int(params.radix_bits[0]) + int(params.radix_bits[1]))
+
+
+def sub_bits(params, n_build):
+    """csrc/phj_capi.hip refine_plan_sub: the bits a too-coarse plan is refined by."""
+    P = requested_partitions(params)
+    expect = n_build / P
+    if expect * 3 <= TCAP * 2:
+        return 0
+    s = 0
+    while expect / (1 << s) > 170.0 and (P - 1).bit_length() + s < 22:
+        s += 1
+    return s
+
+
+class Crowd:
+    """What a crowd case's build side guarantees, asserted on construction."""
+
+    def __init__(self, params, G, rk):
+        self.params, self.G = params, G
+        s = sub_bits(params, len(rk))
+        self.P = requested_partitions(params) << s
+        # fused_setup's precondition: the (refined) partition average within 2/3 of an LDS round
+        assert -(-len(rk) // self.P) <= 170
+        hg = codes(params, G)
+        assert np.array_equal(hg, np.uint64(MATE_BASE) + (np.arange(len(G), dtype=np.uint64) << np.uint64(50)))
+        qg = partition_of(hg, params, s)
+        assert np.all(qg == qg[0]) and np.all(lds_bucket(hg) == np.uint64(93))
+        self.q, self.s = qg[0], s
+        hr = codes(params, rk)
+        mine = partition_of(hr, params, s) == self.q
+        self.m = int(np.count_nonzero(mine))                       # build tuples of the mates' partition
+        self.rounds = -(-self.m // TCAP)
+        strangers = self.m - int(np.count_nonzero(np.isin(rk, G)))   # ... that are no mates
+        # the first round holds min(256, m) of them in some order: all but the
+        # strangers are mates, and mates share a bucket at every round size
+        self.long_bucket = min(TCAP, self.m) - strangers
+        assert self.long_bucket >= WIDE
+
+    def long_probes(self, sk):
+        """Probe keys that can meet the long bucket: those of the mates'
+        partition whose bucket is the mates' at the smallest table (64 buckets)
+        a round with a long bucket can have; and how many 64-tuple groups the
+        partition's probe tuples make (their order is the partitioner's)."""
+        hs = codes(self.params, sk)
+        mine = partition_of(hs, self.params, self.s) == self.q
+        hits = int(np.count_nonzero(mine & (lds_bucket(hs, 64) == np.uint64(93 & 63))))
+        assert hits >= int(np.count_nonzero(np.isin(sk, self.G)))
+        return hits, -(-int(np.count_nonzero(mine)) // 64)
+
+
+@functools.lru_cache(maxsize=None)
+def crowd_case(name, side):
+    """200 mates, 150 of them built (G[3] three times, G[5] 81 times) among
+    1 500 others; probed by at most 16 mate tuples (`few`: the count pass
+    compares the long bucket wave-wide) or by every mate twice (`many`: lane
+    by lane, the emit pass still wave-wide)."""
+    params = BY_NAME[name][1]
+    rng = np.random.default_rng(101)
+    G = partition_mates(params, 200, MATE_BASE)
+    rk = np.concatenate([G[:150], np.repeat(G[3], 2), np.repeat(G[5], 80), filler(rng, 20_000, 1500, G)])
+    rng.shuffle(rk)
+    c = Crowd(params, G, rk)
+    # ... of which at most 82 are further copies: the long bucket holds many distinct keys
+    assert c.long_bucket - 82 >= 32
+    fill = filler(np.random.default_rng(102), 40_000, 3000, G)
+    if side == "few":
+        mates = np.array([G[0], G[3], G[5], G[149], G[150], G[199], G[77], G[3], G[160]])
+        sk = np.concatenate([fill, mates])
+        hits, _ = c.long_probes(sk)
+        assert len(mates) <= hits <= WIDE_LANES      # no 64-tuple group can have more than 16
+    else:
+        mates = np.repeat(G, 2)
+        sk = np.concatenate([fill, mates])
+        hits, groups = c.long_probes(sk)
+        assert len(mates) > WIDE_LANES * groups       # so some 64-tuple group has more than 16
+    np.random.default_rng(103).shuffle(sk)
+    E = Expect(with_payloads(rk, R_BASE), with_payloads(sk, S_BASE))
+    absent = mates[~np.isin(mates, rk)]
+    assert len(absent) >= 2 and np.all(np.isin(absent, G[150:]))
+    assert E.pairs > 81 + 3 and len(E.build_rows) > 0
+    return E, absent
+
+
+@functools.lru_cache(maxsize=None)
+def crowd_rounds_case(name, n_build=600 + 40 + 1500):
+    """600 built mates and 40 more copies of G[7], shuffled: three LDS rounds
+    of one bucket, the copies of one key spread over them (the pairs[s] cursor
+    carried between rounds, with sparse wide compares)."""
+    params = BY_NAME[name][1]
+    rng = np.random.default_rng(201)
+    G = partition_mates(params, 650, MATE_BASE)
+    rk = np.concatenate([G[:600], np.repeat(G[7], 40), filler(rng, 20_000, n_build - 640, G)])
+    rng.shuffle(rk)
+    assert len(rk) == n_build
+    c = Crowd(params, G, rk)
+    assert c.rounds >= 3 if n_build > 2140 else c.rounds == 3
+    # every full round: at least 256 - strangers mates in the one bucket
+    assert c.long_bucket >= WIDE and c.m - 640 < TCAP - WIDE
+    sk = np.concatenate([G[0:600:5], np.repeat(G[7], 3), G[600:], filler(rng, 40_000, 3000, G)])
+    rng.shuffle(sk)
+    E = Expect(with_payloads(rk, R_BASE), with_payloads(sk, S_BASE))
+    assert E.pairs >= 120 + 3 * 41
+    return E, G[600:], c
+
+
+def run_all(ctx, params, ordered, E, classes=CLASSES):
+    """Every join of one case against its expectation; the class-7 rows."""
+    R, S = E.R, E.S
+    ctx.upload(phj.SIDE_BUILD, R)
+    ctx.upload(phj.SIDE_PROBE, S)
+    semi = O.semijoin_count(R, S)
+    assert semi == len(S) - len(E.probe_rows)
+    assert ctx.join(params).matches == semi
+    assert ctx.join_materialize(params).matches == semi
+    check_rows(ctx.joined(), R, S, ordered)
+    assert ctx.join_inner_count(params).matches == E.pairs
+    assert ctx.join_inner(params).matches == E.pairs
+    got = ctx.joined()
+    assert len(got) == E.pairs
+    assert np.array_equal(canon(got), E.pair_rows)
+    pb = got[:, 2]   # the rows of one probe tuple are contiguous
+    assert 1 + int(np.count_nonzero(pb[1:] != pb[:-1])) == len(np.unique(pb))
+    if ordered:
+        assert np.all(pb[1:] >= pb[:-1])
+    full = None
+    for cl in classes:
+        rows = check(ctx, params, ordered, E, cl, upload=False)
+        if cl == 7:
+            full = rows
+    return full
+
+
+def check_absent(full, E, absent):
+    """Probe keys no build tuple has: no pair, one probe-only row per probe tuple."""
+    rows = full[np.isin(full[:, 0], absent)]
+    assert len(rows) == int(np.count_nonzero(np.isin(E.S[:, 0], absent))) > 0
+    assert np.all(rows[:, 1] == NULL) and len(np.unique(rows[:, 2])) == len(rows)
+
+
+def check_build_once(full, E):
+    """Every build tuple stands in the full outer join exactly as often as its
+    key is probed, or once, build-only, when it is not."""
+    asked = {int(k): int(n) for k, n in zip(*np.unique(E.S[:, 0], return_counts=True))}
+    pa, n = np.unique(full[full[:, 1] != NULL, 1], return_counts=True)
+    assert np.array_equal(pa, np.sort(E.R[:, 1]))
+    keys = E.R[np.argsort(E.R[:, 1]), 0]
+    assert np.array_equal(n, [max(1, asked.get(int(k), 0)) for k in keys])
+    lone = full[full[:, 2] == NULL]
+    assert not np.any(np.isin(lone[:, 0], E.S[:, 0]))
+
+
+@pytest.mark.parametrize("side", ["few", "many"])
+@pytest.mark.parametrize("name", RADIX)
+def test_crowd_long_bucket_of_distinct_keys(ctx, name, side):
+    _, params, ordered = BY_NAME[name]
+    E, absent = crowd_case(name, side)
+    full = run_all(ctx, params, ordered, E)
+    check_absent(full, E, absent)
+    check_build_once(full, E)
+    if side == "few":   # the unprobed mates come out build-only
+        G = partition_mates(params, 150, MATE_BASE)
+        quiet = G[~np.isin(G, E.S[:, 0])]
+        lone = full[full[:, 2] == NULL]
+        assert len(quiet) > 100 and np.array_equal(np.sort(lone[np.isin(lone[:, 0], quiet), 0]), np.sort(quiet))
+
+
+@pytest.mark.parametrize("name", RADIX)
+def test_crowd_over_three_rounds(ctx, name):
+    _, params, ordered = BY_NAME[name]
+    E, absent, _ = crowd_rounds_case(name)
+    full = run_all(ctx, params, ordered, E)
+    check_absent(full, E, absent)
+    check_build_once(full, E)
+
+
+@pytest.mark.parametrize("name", RADIX)
+def test_crowd_poisoned_workspace(name):
+    _, params, ordered = BY_NAME[name]
+    with phj.Context(0) as fresh:
+        fresh.debug_poison_alloc(0xFF)
+        check(fresh, params, ordered, crowd_case(name, "few")[0], phj.FULL_OUTER)
+
+
+@functools.lru_cache(maxsize=None)
+def np_edge_case(name, last, first):
+    """70 build tuples homed in one last bucket (40 keys, one of them 31
+    times): 63 of them leave their region through the overflow list and go on
+    from the next region's first bucket, where 10 keys are at home."""
+    params = BY_NAME[name][1]
+    rng = np.random.default_rng(301)
+    A = np_edge_keys(params, last, 60)
+    F = np_edge_keys(params, first, 10)
+    edge = np.concatenate([A, F])
+    rk = np.concatenate([A[:40], np.repeat(A[11], 30), F, filler(rng, 20_000, 300, edge)])
+    rng.shuffle(rk)
+    g = nb, nbr, rbits = np_geometry(len(rk), params.table_ratio)
+    assert rbits >= 1 and nb == nbr << rbits
+    at = {"last_of_table": nb - 1, "last_of_region0": nbr - 1, "first_of_table": 0, "first_of_region1": nbr}
+    assert np.all(np_home(codes(params, A), g) == np.uint64(at[last]))
+    assert np.all(np_home(codes(params, F), g) == np.uint64(at[first]))
+    assert (at[last] + 1) % nb == at[first]            # the run continues where F is at home
+    assert int(np.count_nonzero(np.isin(rk, A))) == 70 > 7   # the last bucket overflows by 63 tuples
+    sk = np.concatenate([rk, A[40:], filler(rng, 40_000, 300, edge)])
+    rng.shuffle(sk)
+    E = Expect(with_payloads(rk, R_BASE), with_payloads(sk, S_BASE))
+    assert E.pairs >= 31 * 31 + 39 + 10 and len(E.build_rows) == 0
+    return E, A[40:]
+
+
+@pytest.mark.parametrize("last,first", [("last_of_table", "first_of_table"), ("last_of_region0", "first_of_region1")],
+                         ids=["wrap", "region-boundary"])
+@pytest.mark.parametrize("name", NP)
+def test_nopart_run_leaves_its_region(ctx, name, last, first):
+    _, params, ordered = BY_NAME[name]
+    E, absent = np_edge_case(name, last, first)
+    full = run_all(ctx, params, ordered, E)
+    check_absent(full, E, absent)
+    check_build_once(full, E)
+
+
+@functools.lru_cache(maxsize=None)
+def full_table_case():
+    """1 400 distinct build keys in 200 buckets of 7: no free slot, no bucket
+    stops a walk (each walk is bounded by the bucket count instead)."""
+    params = BY_NAME["np-murmur-r1"][1]
+    assert params.table_ratio == 1.0
+    rng = np.random.default_rng(401)
+    rk = filler(rng, 20_000, 1400, np.zeros(0, np.int64), distinct=True)
+    nb, nbr, rbits = np_geometry(len(rk), params.table_ratio)
+    assert (nb, nbr, rbits) == (200, 100, 1) and nb * 7 == len(rk) == len(np.unique(rk))
+    sk = np.concatenate([rng.choice(rk, 700, replace=False), filler(rng, 40_000, 200, rk)])
+    rng.shuffle(sk)
+    E = Expect(with_payloads(rk, R_BASE), with_payloads(sk, S_BASE))
+    assert E.pairs == 700 and len(E.probe_rows) == 200 and len(E.build_rows) == 700
+    return E, sk[~np.isin(sk, rk)]
+
+
+def test_nopart_full_table(ctx):
+    _, params, ordered = BY_NAME["np-murmur-r1"]
+    E, absent = full_table_case()
+    full = run_all(ctx, params, ordered, E)
+    check_absent(full, E, absent)
+    check_build_once(full, E)
+
+
+# The chunked, unordered pass 1 (by default from ~134M tuples on): the same
+# expectations as on the default context.
+
+@pytest.mark.parametrize("name", CHUNKED)
+def test_chunked_rows_rounds_case(chunk_ctx, name):
+    _, params, ordered = BY_NAME[name]
+    check(chunk_ctx, params, ordered, rounds_case(), phj.FULL_OUTER)
+
+
+@pytest.mark.parametrize("name", CHUNKED)
+def test_chunked_inner_dup_case(chunk_ctx, name):
+    _, params, ordered = BY_NAME[name]
+    check_dup_case(chunk_ctx, params, ordered)
+
+
+@pytest.mark.parametrize("name", CHUNKED)
+def test_chunked_crowd_over_three_rounds(ctx, chunk_ctx, name):
+    _, params, ordered = BY_NAME[name]
+    E, absent, c = crowd_rounds_case(name, 4000)
+    if name == "radix-4":   # 250 build tuples per requested partition: refined, two passes
+        assert len(E.R) > 16 * 170 and c.s == 1
+    full = run_all(chunk_ctx, params, ordered, E)
+    check_absent(full, E, absent)
+    check_build_once(full, E)
+    # the default context gives the same rows
+    assert np.array_equal(canon(check(ctx, params, ordered, E, phj.FULL_OUTER)), canon(full))
