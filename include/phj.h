@@ -446,6 +446,18 @@ int phj_debug_poison_chunk_table(phj_ctx *ctx, int side, const phj_join_params *
  * cleared or written by the library itself, so every count stays exact. */
 int phj_debug_poison_alloc(phj_ctx *ctx, int byte);
 
+/* ---- test hook: hot-key pre-aggregation ----
+ * Replaces nothing in the reference. phj_join's counting LDS join, in its
+ * default schedule on one device, samples the probe side, counts its hottest
+ * keys in pass 1 instead of writing them, and resolves them against the build
+ * side in the build side's pass 1. `mode` sets when: 0 auto (probe sides of
+ * 16.8M tuples and more, and only a table covering an eighth of the sample),
+ * 1 off, 2 forced (any size, the lowest sample threshold, any coverage), -1
+ * leaves the mode as it is. `stats` (may be null) receives the last phj_join's
+ * {entries of the hot table, probe tuples pre-aggregated}: both 0 when that
+ * join did not take the path. A multi-device or rank context never takes it. */
+int phj_debug_preagg(phj_ctx *ctx, int mode, uint64_t *stats);
+
 /* ---- test hook: a failing rank ----
  * Replaces nothing in the reference. On a multi-device or rank context, local
  * member `member` (-1: none) fails the next phj_join before the exchange. The

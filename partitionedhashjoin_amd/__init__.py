@@ -31,6 +31,7 @@ PART_STABLE = 0x1   # include/phj.h PHJ_PART_STABLE
 TABLE_CHAINED = 0x2   # include/phj.h PHJ_TABLE_CHAINED
 DEFER_TIMERS = 0x4   # include/phj.h PHJ_DEFER_TIMERS: timers read later by Context.timers_report()
 LEAN_TIMERS = 0x8    # include/phj.h PHJ_LEAN_TIMERS: only the critical path's large kernels timed
+PREAGG_AUTO, PREAGG_OFF, PREAGG_FORCED = 0, 1, 2   # include/phj.h phj_debug_preagg's modes
 
 
 def radix_params(bits=(8, 8), num_partitions=0, hash=HASH_MURMUR3, seed=DEFAULT_SEED,
@@ -359,6 +360,15 @@ class Context:
         context (and each of its members) allocates from now on is filled with
         `byte` (-1: off), so a read of a word nothing wrote shows."""
         self._check(self._L.phj_debug_poison_alloc(self._h, byte))
+
+    def debug_preagg(self, mode: int = -1) -> tuple:
+        """Test hook (phj_debug_preagg): set when phj_join pre-aggregates hot
+        probe keys (PREAGG_AUTO / PREAGG_OFF / PREAGG_FORCED; -1 keeps the
+        mode) and return the last join's (hot entries, pre-aggregated probe
+        tuples), both 0 when it did not take that path."""
+        stats = (C.c_uint64 * 2)()
+        self._check(self._L.phj_debug_preagg(self._h, mode, stats))
+        return int(stats[0]), int(stats[1])
 
     def debug_fail_member(self, member: int) -> None:
         """Test hook (phj_debug_fail_member): local member `member` fails the

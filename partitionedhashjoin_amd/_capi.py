@@ -41,6 +41,7 @@ EXPORTED = [
     "phj_ctx_info", "phj_shard_range", "phj_probe_pass1", "phj_debug_poison_chunk_table", "phj_debug_poison_alloc", "phj_debug_fail_member", "phj_debug_exchange_block", "phj_exchange_geometry",
     "phj_exchange_layout", "phj_count_contribution", "phj_count_verdict", "phj_join_path",
     "phj_join_inner_count", "phj_join_inner", "phj_join_rows_count", "phj_join_rows",
+    "phj_debug_preagg",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
@@ -153,6 +154,7 @@ def load():
         "phj_probe_pass1": (i, [P, P, P, u64, P, P, P]),
         "phj_debug_poison_chunk_table": (i, [P, i, P, i]),
         "phj_debug_poison_alloc": (i, [P, i]),
+        "phj_debug_preagg": (i, [P, i, C.POINTER(u64)]),
         "phj_debug_fail_member": (i, [P, i]),
         "phj_debug_exchange_block": (i, [P, i, P, u64]),
         "phj_exchange_geometry": (i, [P, u64, P, P, P, P, P]),

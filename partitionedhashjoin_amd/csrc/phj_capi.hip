@@ -24,6 +24,10 @@
 
 // Measurement builds only (scripts/ab_lib.sh, `make prof-lib`): the phase-clock
 // forms of S's pass 1 and of the LDS join's builds, printed to stderr per join.
+// 0: an A/B build without the hot-key pre-aggregation (phj_hot.h; scripts/ab_lib.sh)
+#ifndef PHJ_PREAGG
+#define PHJ_PREAGG 1
+#endif
 #ifndef PHJ_P1_PROF
 #define PHJ_P1_PROF 0
 #endif
@@ -38,6 +42,7 @@
 #include "phj_outer.h"
 #include "phj_mat.h"
 #include "phj_partition.h"
+#include "phj_hot.h"
 #include "phj_table.h"
 
 using namespace phj;
@@ -212,6 +217,14 @@ struct phj_ctx {
     void* s_zero_pending = nullptr;
     size_t s_zero_pending_bytes = 0;
     int poison = -1;   // phj_debug_poison_alloc: every new workspace buffer is filled with this byte
+    // hot-key pre-aggregation (phj_hot.h): the state; phj_debug_preagg's mode
+    // (0 auto, 1 off, 2 forced); hot_on: the running join's code passes take
+    // their HOT forms; hot_ran / hot_n / hot_min_mass: the last join's, for its statistics
+    DevBuf hot;
+    int hot_mode = 0;
+    bool hot_on = false, hot_ran = false;
+    uint64_t hot_n = 0;
+    uint32_t hot_min_mass = 0;
 };
 
 namespace {
@@ -643,7 +656,11 @@ int scan_u32(phj_ctx* c, uint32_t* data, uint32_t len, uint32_t narrays, uint32_
 // flight (S: 2, measured 1.08 -> 1.05 ms at C2; R: 1); a measurement build
 // (-DPHJ_P1_PROF=1, scripts/ab_lib.sh) runs S's pass in the phase-clock form.
 template <int HK, int DPT>
-const void* pipe1024(int kpf) {
+const void* pipe1024(int kpf, bool hot = false) {
+    if constexpr (DPT == 1 && PHJ_PREAGG != 0) {   // the HOT forms (phj_hot.h): S's counts weights, R's resolves them
+        if (hot && kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 2>);
+        if (hot) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 1>);
+    }
     if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, false, 1>);
     return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, PHJ_P1_PROF != 0, 2>);
 }
@@ -701,7 +718,10 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
             const uint32_t ntiles = static_cast<uint32_t>((n + T - 1) / T);
             const uint32_t per = (ntiles + a.nshards - 1) / a.nshards;
             const bool pipe = a.keys_only && c->tune.p1_pipe && BLOCK == 512 && ITEMS == 8;
-            const size_t lds = pipe ? chunk_pipe_lds_bytes(T, a.nbins) : a.keys_only ? chunk_codes_lds_bytes(T, a.nbins) : sc_lds;
+            const bool is_r = prefix.rfind("R.", 0) == 0;
+            const bool hot = a.hot_code != nullptr;   // (the host offers it only where the 1024 x 4, one-digit-per-thread form runs)
+            const size_t lds = pipe ? chunk_pipe_lds_bytes(T, a.nbins) + chunk_pipe_hot_lds_bytes(a.nbins, hot ? (is_r ? 2 : 1) : 0)
+                               : a.keys_only ? chunk_codes_lds_bytes(T, a.nbins) : sc_lds;
             const void* kfn = nullptr;
             int kblock = BLOCK;
             // keys only, written as hash codes (the on-chip probe): k_chunk_codes;
@@ -715,11 +735,14 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                         // R's pass (LDS join, tile mode: ~10 tiles per workgroup at C2)
                         // keeps one tile in flight, which also gives it a kernel name of
                         // its own in rocprof summaries (S's is the roofline kernel)
-                        const int kpf = prefix.rfind("R.", 0) == 0 ? 1 : 2;
+                        const int kpf = is_r ? 1 : 2;
+                        if (hot && dpt == 4) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation: more digits than threads");
                         kfn = with_hash(hk, [&](auto h) {
                             constexpr int HK = decltype(h)::value;
-                            return dpt == 4 ? pipe1024<HK, 2>(kpf) : pipe1024<HK, 1>(kpf);
+                            return dpt == 4 ? pipe1024<HK, 2>(kpf) : pipe1024<HK, 1>(kpf, hot);
                         });
+                    } else if (hot) {
+                        return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs the 1024-thread code pass");
                     } else
                         kfn = with_hash(hk, [&](auto h) {
                             constexpr int HK = decltype(h)::value;
@@ -761,7 +784,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
             if (c->tune.p1_slots > 0) slots = std::min<uint32_t>(per, c->tune.p1_slots);
             if (c->tune.p1_slots < 0) slots = per;   // one tile per workgroup
             PassArgs ak = a;
-            const bool prof = PHJ_P1_PROF && pipe && kblock == 1024 && prefix.rfind("R.", 0) != 0;
+            const bool prof = PHJ_P1_PROF && pipe && kblock == 1024 && !is_r && !hot;
             if (prof) {   // diagnostics (measurement build, PHJ_P1_PROF): synchronous, to stderr
                 PHJ_TRY(ensure(c, c->cl_prof, 64 * 8));   // words 32.. (the LDS join's are 0..)
                 ak.prof = static_cast<unsigned long long*>(c->cl_prof.p) + 32;
@@ -1005,6 +1028,17 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
         S.ctab_dirty = n > 0;   // until k_tile_chunks has cleared what pass 1 publishes
         S.chunk_check = n > 0;
     }
+    unsigned long long* kept = nullptr;   // S's pre-aggregating pass: the tuples it wrote
+    if (c->hot_on) {   // phj_join's counting LDS join, default schedule (hot_begin)
+        if (!S.hcoded) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs the chunked code pass");
+        uint32_t* st = static_cast<uint32_t*>(c->hot.p);
+        a.hot_code = reinterpret_cast<const unsigned long long*>(st + kHotCounters);
+        a.hot_w = reinterpret_cast<unsigned long long*>(st + kHotCounters) + static_cast<size_t>(pl.nb1) * kHotPer;
+        a.hot_ctl = reinterpret_cast<const uint32_t*>(a.hot_w + static_cast<size_t>(pl.nb1) * kHotPer);
+        a.hot_min_mass = c->hot_min_mass;
+        a.hot_count = static_cast<unsigned long long*>(c->count.p);
+        if (&S == &c->side[PHJ_SIDE_PROBE]) kept = reinterpret_cast<unsigned long long*>(const_cast<uint32_t*>(a.hot_ctl) + 2);
+    }
     uint32_t* tb2 = pl.npass == 2 ? static_cast<uint32_t*>(S.tbase2.p) : nullptr;
     PHJ_TRY(launch_pass(c, pl.hk, true, p1_aos, a, nt1, std::string(tag) + ".p1", n, nt1 * pl.nb1));
     if (chunked) {
@@ -1016,7 +1050,7 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
         }
         {
             hipLaunchKernelGGL(k_pass1_finish_sizes, dim3(1), dim3(kFinSizesBlock), 0, c->ks, a.chunk_cursor, pl.nb1, nshards, n, tile2,
-                               static_cast<uint32_t*>(S.bounds1.p), tb2, zero, clr, static_cast<uint32_t>(c->p1_clear_bytes / 16));
+                               static_cast<uint32_t*>(S.bounds1.p), tb2, zero, clr, static_cast<uint32_t>(c->p1_clear_bytes / 16), kept);
             PHJ_LAUNCHED(c, "k_pass1_finish_sizes");
         }
     } else {
@@ -1098,6 +1132,71 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
 // or null
 int partition_side(phj_ctx* c, int s, const Plan& pl, bool p1_only = false, unsigned long long* zero = nullptr) {
     return partition_state(c, c->side[s], s == PHJ_SIDE_BUILD ? "R" : "S", pl, p1_only, zero);
+}
+
+// Hot-key pre-aggregation (phj_hot.h) for phj_join's counting LDS join in its
+// default schedule (R's chain in tile mode after S's pass on the main stream):
+// whether this join takes it. A host-side decision: both code passes must be
+// the 1024 x 4 pipelined form with one digit per thread (the LDS holds the
+// table beside the pass's own 90 KB up to 1024 clusters), R's pass must be the
+// one that resolves the weights, and S must be large enough that the sample
+// (kHotTiles tiles, two reads) is small against its pass: 32 times the sample.
+constexpr uint64_t kHotMinS = 32ull * kHotTiles * kHotTile;   // 16.8M tuples
+bool hot_wanted(const phj_ctx* c, const Plan& cpl, uint64_t nS, uint64_t nR) {
+    if (!PHJ_PREAGG || c->hot_mode == 1 || c->dry || nS == 0) return false;
+    if (c->tune.r_order != 1 || !c->tune.r_chunk || !c->tune.p1_pipe || c->tune.p1_block != 1024) return false;
+    const TileShape sh = tile_shape(c, cpl.nb1);
+    if (sh.block != 512 || sh.tile != 4096 || cpl.nb1 > 1024) return false;
+    if (!chunked_pass1(c, cpl, nS, true) || (nR > 0 && !chunked_pass1(c, cpl, nR, true))) return false;
+    if (cluster_empty0(cpl) == 0) return false;   // one cluster: no code marks an empty way
+    return c->hot_mode == 2 || nS >= kHotMinS;
+}
+
+// The sample and the selection, on the main stream before S's pass 1; the
+// code passes of this join then take their HOT forms (c->hot_on). Forced
+// mode (phj_debug_preagg) takes the lowest threshold and any coverage.
+int hot_begin(phj_ctx* c, const Plan& cpl, const SideState& S) {
+    PHJ_TRY(ensure(c, c->hot, hot_state_bytes(cpl.nb1)));
+    const bool forced = c->hot_mode == 2;
+    HotArgs h{};
+    h.rel = reinterpret_cast<const int64_t*>(S.rel);
+    h.n = static_cast<uint32_t>(S.n);
+    h.ntiles = (h.n + kHotTile - 1) / kHotTile;
+    h.nsamp = std::min(kHotTiles, h.ntiles);
+    h.thr = forced ? 2u : std::max(2u, kHotThreshold * h.nsamp / kHotTiles);
+    h.f = digit_fn(cpl, 1);
+    h.nb = cpl.nb1;
+    h.e0 = cluster_empty0(cpl);
+    h.counters = static_cast<uint32_t*>(c->hot.p);
+    h.code = reinterpret_cast<unsigned long long*>(h.counters + kHotCounters);
+    h.w = h.code + static_cast<size_t>(cpl.nb1) * kHotPer;
+    h.ctl = reinterpret_cast<uint32_t*>(h.w + static_cast<size_t>(cpl.nb1) * kHotPer);
+    // a table covering under an eighth of the sample is ignored by both passes
+    c->hot_min_mass = forced ? 0u : static_cast<uint32_t>(std::min<uint64_t>(S.n, static_cast<uint64_t>(h.nsamp) * kHotTile) / 8);
+    c->hot_n = S.n;
+    // no timer events under PHJ_LEAN_TIMERS (each one between two kernels costs ~4 us)
+    const bool timed = !c->lean_timers;
+    if (timed) PHJ_TRY(timer_begin(c, "S.hot", 2ull * h.nsamp * kHotTile * 16));
+    const void* ksample = with_hash(cpl.hk, [](auto hh) { return reinterpret_cast<const void*>(&k_hot_sample<decltype(hh)::value>); });
+    const void* kselect = with_hash(cpl.hk, [](auto hh) { return reinterpret_cast<const void*>(&k_hot_select<decltype(hh)::value>); });
+    // auto mode: a first look at an eighth of the sample's tiles; without skew there the rest returns at once
+    h.staged = !forced && h.nsamp == kHotTiles ? 1u : 0u;
+    hipLaunchKernelGGL(k_hot_clear, dim3(16), dim3(kHotBlock), 0, c->ks, h);
+    PHJ_LAUNCHED(c, "k_hot_clear");
+    uint32_t phase = h.staged ? 1u : 0u;
+    void* sargs[] = {&h, &phase};
+    const uint32_t first = h.staged ? (h.nsamp + kHotStage - 1) / kHotStage : h.nsamp;
+    PHJ_TRY(launch_kernel(c, ksample, dim3(first), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
+    if (h.staged) {
+        phase = 2;
+        PHJ_TRY(launch_kernel(c, ksample, dim3(h.nsamp), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
+    }
+    void* kargs[] = {&h};
+    PHJ_TRY(launch_kernel(c, kselect, dim3(h.nsamp), dim3(kHotBlock), kargs, 0, "k_hot_select"));
+    if (timed) PHJ_TRY(timer_end(c));
+    c->hot_on = true;
+    c->hot_ran = true;
+    return PHJ_OK;
 }
 
 // Build over `nseg` partitioned build segments and probe the ctx's partitioned
@@ -2746,7 +2845,7 @@ void phj_ctx_destroy(phj_ctx* c) {
             free_buf(*b);
     }
     for (DevBuf* b : {&c->ht_tab, &c->ht_desc, &c->r_codes, &c->r_bounds, &c->scan_partials, &c->prep, &c->tkeys, &c->tpays, &c->toffs, &c->gcursor, &c->items, &c->biglist,
-                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->cl_done})
+                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->cl_done, &c->hot})
         free_buf(*b);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
@@ -3010,6 +3109,7 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     c->lean_timers = (p->flags & PHJ_LEAN_TIMERS) != 0;
     c->timer_skipped = false;
     c->count_pinned = false;
+    c->hot_ran = false;
     if (!c->defer_timers || c->timers.size() > kMaxTimerRecs) reset_timers(c);
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) return join_nopart(c, p, r);
     if (p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
@@ -3090,6 +3190,14 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
             c->p1_clear = R.ccur.p;
             c->p1_clear_bytes = chunk_state_bytes(cpl.nb1);
         }
+        // hot probe keys (phj_hot.h): sampled and selected here; S's pass then
+        // counts them instead of writing them, R's pass adds their weights to
+        // the count (after S's bookkeeping kernel has cleared it: one stream)
+        struct HotScope {
+            phj_ctx* c;
+            ~HotScope() { c->hot_on = false; }
+        } hot_scope{c};
+        if (hot_wanted(c, cpl, S.n, R.n)) PHJ_TRY(hot_begin(c, cpl, S));
         const int prc = partition_side(c, PHJ_SIDE_PROBE, cpl, true, static_cast<unsigned long long*>(c->count.p));
         c->p1_clear = nullptr;
         if (prc != PHJ_OK) {
@@ -3231,6 +3339,7 @@ int phj_prepare(phj_ctx* c, const phj_join_params* p) {
     PHJ_TRY(make_plan(c, p, pl));
     if (use_cluster(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n, cpl)) {
         const uint64_t nR = c->side[PHJ_SIDE_BUILD].n;
+        if (PHJ_PREAGG) PHJ_TRY(ensure(c, c->hot, hot_state_bytes(cpl.nb1)));
         PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, cpl, true));
         PHJ_TRY(ensure(c, c->r_codes, std::max<uint64_t>(1, nR) * 8));
         PHJ_TRY(ensure(c, c->r_bounds, (static_cast<size_t>(cpl.nb1) + 1) * 4));
@@ -3464,6 +3573,31 @@ int phj_debug_poison_alloc(phj_ctx* c, int byte) {
     c->poison = v;
     if (c->group)
         for (int i = 0; i < c->group->nlocal(); i++) c->group->mem[i]->poison = v;
+    return PHJ_OK;
+}
+
+int phj_debug_preagg(phj_ctx* c, int mode, uint64_t* stats) {
+    if (!c) return PHJ_ERR_INVALID;
+    if (mode < -1 || mode > 2) return set_err(c, PHJ_ERR_INVALID, "mode is -1 (keep), 0 (auto), 1 (off) or 2 (forced)");
+    if (stats) stats[0] = stats[1] = 0;
+    if (c->group) return PHJ_OK;   // the member step does not pre-aggregate
+    if (stats && c->hot_ran && c->hot.p) {
+        (void)hipGetLastError();
+        PHJ_HIP(c, hipSetDevice(c->device));
+        PHJ_HIP(c, hipStreamSynchronize(c->stream));
+        struct {
+            uint32_t entries, mass;
+            unsigned long long kept;
+        } h{};
+        const char* ctl = static_cast<const char*>(c->hot.p) + static_cast<size_t>(kHotCounters) * 4 +
+                          static_cast<size_t>(c->side[PHJ_SIDE_PROBE].plan.nb1) * kHotPer * 16;
+        PHJ_HIP(c, hipMemcpy(&h, ctl, sizeof(h), hipMemcpyDeviceToHost));
+        if (h.entries != 0 && h.mass >= c->hot_min_mass) {   // the passes' own test
+            stats[0] = h.entries;
+            stats[1] = c->hot_n - h.kept;
+        }
+    }
+    if (mode >= 0) c->hot_mode = mode;
     return PHJ_OK;
 }
 

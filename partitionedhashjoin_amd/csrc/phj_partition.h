@@ -139,8 +139,24 @@ struct PassArgs {
     unsigned long long* sink;   // k_chunk_codes: [kSinkGroups][BLOCK] words the stores past the tile target (never read)
     DigitFn f;
     unsigned long long* prof;   // k_chunk_codes_pipe PROF: clocks of its phases, kP1ProfWords (diagnostics)
+    // k_chunk_codes_pipe HOT (phj_hot.h): the hot table of this join's probe
+    // side, [nbins][kHotPer] codes and 64-bit weights, its control words
+    // (kHotCtl*), the sample mass below which the table is ignored, and (R's
+    // pass) the join's count word
+    const unsigned long long* hot_code;
+    unsigned long long* hot_w;
+    const uint32_t* hot_ctl;
+    uint32_t hot_min_mass;
+    unsigned long long* hot_count;
 };
 constexpr int kP1ProfWords = 16;
+// the hot table: every digit has kHotSub sets (chosen by the code's top bit)
+// of kHotWays ways, so a lookup is one 16-B LDS read
+constexpr uint32_t kHotWays = 2, kHotSub = 2, kHotPer = kHotWays * kHotSub;
+#ifndef PHJ_HOT_AGG   // (a measurement build may aggregate the weight adds per wave: DESIGN.md section 3)
+#define PHJ_HOT_AGG 0
+#endif
+constexpr uint32_t kHotCtlEntries = 0, kHotCtlMass = 1;   // hot_ctl words: entries, sampled keys they cover
 
 // Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md,
 // "Workgroup dispatch"); with xcd_remap each XCD instead walks a contiguous
@@ -1111,6 +1127,11 @@ __device__ __forceinline__ unsigned long long pipe_hint(uint32_t j, uint32_t rid
 __host__ __device__ constexpr size_t chunk_pipe_lds_bytes(int T, uint32_t nb) {
     return 2 * static_cast<size_t>(T) * 8 + (static_cast<size_t>(2 * nb + 3) / 4 * 4 + 4 * static_cast<size_t>(nb)) * 4 + 128;
 }
+// ... and after them the HOT forms' copy of the hot table: the codes, and
+// (HOT 1) the workgroup's 32-bit weights and a word per thread (1024 of them)
+__host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int hot) {
+    return hot == 0 ? 0 : static_cast<size_t>(nb) * kHotPer * (hot == 1 ? 12 : 8) + (hot == 1 ? 4096 : 0);
+}
 
 // Registers: one workgroup per CU (LDS). WPE: waves per SIMD the registers
 // must allow (0: the workgroup's own, BLOCK / 256; 1024 x 4 held to 5, <= 96
@@ -1120,7 +1141,18 @@ __host__ __device__ constexpr size_t chunk_pipe_lds_bytes(int T, uint32_t nb) {
 // claims + B2, scatter + protocol, B3, write-out, then the tiles, and each
 // wave's time from a barrier to the next (max / mean over the waves)
 // (diagnostics; a barrier's time is wave 0's wait for the slowest wave).
-template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1>
+// HOT (phj_hot.h; the counting LDS join's default schedule): the workgroup
+// keeps the probe side's hot table in LDS and looks every code up in the set
+// of its digit. 1 (S's pass): a code found there adds 1 to its entry's LDS
+// weight and is neither ranked nor written, so a tile's valid count is the
+// scan's total of kept codes; the workgroup adds its weights to the global
+// ones when it ends. 2 (R's pass, after S's on the same stream): a code found
+// there takes the entry's global weight by an exchange with 0 (a key R holds
+// twice counts once, as the probe's set test) and adds it to the count; the
+// code is written as ever. A table with no entries, or covering less than
+// hot_min_mass sampled keys, skips the lookups (workgroup-uniform, and the
+// same in both passes: they read the same words).
+template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : BLOCK / 256)))
 void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     constexpr int NW = BLOCK / 64;
@@ -1132,6 +1164,9 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     uint32_t* wcnt = reinterpret_cast<uint32_t*>(sbuf + 2 * T);             // [2][nb] counter rows
     uint4* wdesc = reinterpret_cast<uint4*>(wcnt + (2 * nb + 3u) / 4 * 4);  // [nb] {k < split: slot - k, else, split}
     uint32_t* tmp = reinterpret_cast<uint32_t*>(wdesc + nb);                // [0, NW) scan; 16-19 reservations [2]; 20 bad tile
+    unsigned long long* hcode = reinterpret_cast<unsigned long long*>(tmp + 32);   // HOT: [nb][kHotPer] codes
+    uint32_t* hwt = reinterpret_cast<uint32_t*>(hcode + static_cast<size_t>(nb) * kHotPer);   // HOT 1: their weights in this workgroup
+    uint32_t* hown = hwt + static_cast<size_t>(nb) * kHotPer;   // HOT 1: [BLOCK] a word per lane for the adds of 0
 
     const uint32_t x = blockIdx.x % a.nshards, slots = gridDim.x / a.nshards;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1215,6 +1250,15 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
         const uint32_t t = tile + f * slots;
         load(key[f], t < t_end ? t : tile);
     }
+    bool hot = false;   // workgroup-uniform
+    if constexpr (HOT != 0) {
+        hot = a.hot_ctl[kHotCtlEntries] != 0 && a.hot_ctl[kHotCtlMass] >= a.hot_min_mass;
+        if (hot)
+            for (uint32_t i = tid; i < nb * kHotPer; i += BLOCK) {
+                hcode[i] = a.hot_code[i];
+                if constexpr (HOT == 1) hwt[i] = 0;
+            }
+    }
     {
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
@@ -1254,6 +1298,8 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
         const uint32_t next = tile + slots;
         int64_t code[ITEMS];
         uint32_t dig[ITEMS], rank[ITEMS];
+        uint32_t keep = 0;    // HOT: bit i = item i is ranked and written
+        uint32_t kept = cnt;  // the tile's codes that are (HOT 1: the scan's total)
         if (live) {
             // full: a whole tile (every lane valid; the checks compiled out).
             // The loads stay outside the forms: one instance, straight into
@@ -1273,8 +1319,61 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             else hash_all(F0{}, std::false_type{});
             const uint32_t ahead = tile + KPF * slots;
             load(key[kb], ahead < t_end ? ahead : tile);
+            if constexpr (HOT != 0) {
 #pragma unroll
-            for (int i = 0; i < ITEMS; i++) rank[i] = atomicAdd(&crow[dig[i]], wbase + i * 64 + lane < cnt ? 1u : 0u);
+                for (int i = 0; i < ITEMS; i++) keep |= (wbase + i * 64 + lane < cnt ? 1u : 0u) << i;
+                if (hot) {
+                    // every set read first, then the compares: no branch per
+                    // code (a branch waits for its own LDS read: four round
+                    // trips a tile, measured +0.04 ms on S's pass)
+                    static_assert(kHotWays == 2, "a set is one 16-B read");
+                    static_assert(HOT != 1 || BLOCK <= 1024, "chunk_pipe_hot_lds_bytes: a word per thread");
+                    uint4 set[ITEMS];
+                    uint32_t e[ITEMS];
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) {
+                        e[i] = dig[i] * kHotPer + static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 63) * kHotWays;
+                        set[i] = *reinterpret_cast<const uint4*>(hcode + e[i]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) {
+                        const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
+                        const bool m0 = set[i].x == lo && set[i].y == hi, m1 = set[i].z == lo && set[i].w == hi;
+                        const bool m = (m0 || m1) && ((keep >> i) & 1u) != 0;
+                        const uint32_t ew = e[i] + (m0 ? 0u : 1u);
+                        if constexpr (HOT == 1) {
+                            // (a lane without a match adds 0 to a word of its own)
+#if PHJ_HOT_AGG   // measurement build: the lanes sharing the first matching lane's entry add once
+                            const uint64_t act = __ballot(m);
+                            const int leader = act ? __builtin_ctzll(act) : 0;
+                            const uint32_t lew = __builtin_amdgcn_readlane(ew, leader);
+                            const bool same = m && ew == lew;
+                            const uint32_t nsame = static_cast<uint32_t>(__popcll(__ballot(same)));
+                            const bool lead = same && lane == static_cast<uint32_t>(leader);
+                            atomicAdd(lead ? &hwt[lew] : m && !same ? &hwt[ew] : &hown[tid], lead ? nsame : m && !same ? 1u : 0u);
+#else
+                            atomicAdd(m ? &hwt[ew] : &hown[tid], m ? 1u : 0u);
+#endif
+                            keep &= ~((m ? 1u : 0u) << i);
+                        } else if (m) {
+                            const unsigned long long got = atomicExch(&a.hot_w[ew], 0ull);
+                            if (got) atomicAdd(a.hot_count, got);
+                        }
+                    }
+                }
+            }
+            if constexpr (HOT == 1) {
+                // (a dropped code claims no rank: 0 added to the lane's own word, not
+                // to its digit's counter, where a hot key's lanes would still queue)
+#pragma unroll
+                for (int i = 0; i < ITEMS; i++) {
+                    const bool k = ((keep >> i) & 1u) != 0;
+                    rank[i] = atomicAdd(k ? &crow[dig[i]] : &hown[tid], k ? 1u : 0u);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < ITEMS; i++) rank[i] = atomicAdd(&crow[dig[i]], wbase + i * 64 + lane < cnt ? 1u : 0u);
+            }
         }
         ptick(0);
         parrive(0);
@@ -1291,6 +1390,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             }
             uint32_t total;
             uint32_t run = block_exclusive_scan_t<NW, false>(local, tmp, total);
+            if constexpr (HOT == 1) kept = __builtin_amdgcn_readfirstlane(total);   // (uniform: the write-out's form is a scalar branch)
 #pragma unroll
             for (int j = 0; j < DPT; j++) {
                 ds[j] = run;
@@ -1329,7 +1429,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             for (int i = 0; i < ITEMS; i++) base[i] = crow[dig[i]];
 #pragma unroll
             for (int i = 0; i < ITEMS; i++)
-                if (wbase + i * 64 + lane < cnt) sbuf[par * T + base[i] + rank[i]] = code[i];
+                if (HOT == 1 ? ((keep >> i) & 1u) != 0 : wbase + i * 64 + lane < cnt) sbuf[par * T + base[i] + rank[i]] = code[i];
         }
         const uint32_t pp = par ^ 1u;   // the previous tile's buffers
         // the next tile's counter row: the previous tile's, no longer read
@@ -1416,16 +1516,22 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             auto write_out = [&](auto form, auto full) {
                 int64_t v[ITEMS];
                 uint32_t o[ITEMS];
+                // (HOT 1: a tile that kept few codes skips the slot groups past them,
+                // workgroup-uniform: neither read from LDS nor stored to the sink)
+                auto past = [&](int i) { return HOT == 1 && !decltype(full)::value && static_cast<uint32_t>(i) * BLOCK >= lim; };
 #pragma unroll
-                for (int i = 0; i < ITEMS; i++) v[i] = sbuf[pp * T + i * BLOCK + tid];
+                for (int i = 0; i < ITEMS; i++)
+                    if (!past(i)) v[i] = sbuf[pp * T + i * BLOCK + tid];
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
+                    if (past(i)) continue;
                     const uint32_t k = i * BLOCK + tid;
                     const uint4 w = wdesc[code_digit(static_cast<uint64_t>(v[i]), form)];
                     o[i] = (k < w.z ? w.x : w.y) + k;
                 }
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
+                    if (past(i)) continue;
                     if constexpr (decltype(full)::value) a.out_keys[o[i]] = v[i];
                     else *(i * BLOCK + tid < lim ? a.out_keys + o[i] : ssink) = v[i];
                 }
@@ -1447,7 +1553,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             pc[j] = c[j];
             pds[j] = ds[j];
         }
-        pcnt = cnt;
+        pcnt = kept;
         have_prev = true;
         tile = next;
         par ^= 1u;
@@ -1462,6 +1568,14 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     } else {
         while (iter(I0{}, I0{}) && iter(I1{}, I1{})) {
         }
+    }
+    if constexpr (HOT == 1) {
+        // (every weight add is before a barrier of the drained iteration)
+        if (hot)
+            for (uint32_t i = tid; i < nb * kHotPer; i += BLOCK) {
+                const uint32_t w = hwt[i];
+                if (w) atomicAdd(&a.hot_w[i], static_cast<unsigned long long>(w));
+            }
     }
 }
 
@@ -1675,12 +1789,13 @@ __global__ __launch_bounds__(kBlock) void k_tile_chunks(const uint32_t* tile_bas
 // over the shards: the segments' offsets in the pass-2 output) and
 // tile_base2 = exclusive scan of their chunk counts; `zero` (may be null: four
 // words) and `clr` (may be null: clr16 16-B words, another pass's chunk state)
-// are cleared. One workgroup.
+// are cleared. `kept` (may be null): the tuples the pass wrote, which the
+// pre-aggregating code pass (k_chunk_codes_pipe HOT) leaves below n. One workgroup.
 constexpr uint32_t kFinSizesBlock = 1024;   // one digit per thread at 1024 clusters: one round of shard loads
 __global__ __launch_bounds__(kFinSizesBlock) void k_pass1_finish_sizes(const uint32_t* sizes, uint32_t nb, uint32_t nshards,
                                                                        uint32_t n, uint32_t T, uint32_t* bounds1,
                                                                        uint32_t* tile_base2, unsigned long long* zero,
-                                                                       uint4* clr, uint32_t clr16) {
+                                                                       uint4* clr, uint32_t clr16, unsigned long long* kept) {
     constexpr uint32_t B = kFinSizesBlock;
     __shared__ uint32_t wsum[2][B / 64];
     const uint32_t tid = threadIdx.x;
@@ -1712,6 +1827,7 @@ __global__ __launch_bounds__(kFinSizesBlock) void k_pass1_finish_sizes(const uin
     if (tid == 0) {
         bounds1[nb] = n;
         tile_base2[nb] = cy;
+        if (kept) *kept = cx;
     }
 }
 
