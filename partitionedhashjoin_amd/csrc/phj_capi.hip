@@ -28,6 +28,15 @@
 #ifndef PHJ_PREAGG
 #define PHJ_PREAGG 1
 #endif
+// 1: with the hot-key pre-aggregation, R's chain runs on the aux stream beside
+// the hot-key prologue, on all but PHJ_HOT_FREE_CUS CUs per shard of its pass 1;
+// 0: after S's pass 1 on the main stream (the A/B leg, scripts/ab_lib.sh)
+#ifndef PHJ_HOT_EARLY_R
+#define PHJ_HOT_EARLY_R 1
+#endif
+#ifndef PHJ_HOT_FREE_CUS
+#define PHJ_HOT_FREE_CUS 6
+#endif
 #ifndef PHJ_P1_PROF
 #define PHJ_P1_PROF 0
 #endif
@@ -218,13 +227,19 @@ struct phj_ctx {
     size_t s_zero_pending_bytes = 0;
     int poison = -1;   // phj_debug_poison_alloc: every new workspace buffer is filled with this byte
     // hot-key pre-aggregation (phj_hot.h): the state; phj_debug_preagg's mode
-    // (0 auto, 1 off, 2 forced); hot_on: the running join's code passes take
-    // their HOT forms; hot_ran / hot_n / hot_min_mass: the last join's, for its statistics
+    // (0 auto, 1 off, 2 forced); hot_on: the running join's probe-side code
+    // pass takes its HOT form; hot_ran / hot_n / hot_min_mass: the last join's, for its statistics
     DevBuf hot;
     int hot_mode = 0;
     bool hot_on = false, hot_ran = false;
     uint64_t hot_n = 0;
     uint32_t hot_min_mass = 0;
+    // R's chain beside the hot-key prologue (PHJ_HOT_EARLY_R): the aux stream
+    // waits for hot_fork (the main stream at the join's start), the main
+    // stream for hot_join (the end of R's chain); p1_free_cus: CUs per shard
+    // the chunked pass 1 launched next leaves free
+    hipEvent_t hot_fork = nullptr, hot_join = nullptr;
+    uint32_t p1_free_cus = 0;
 };
 
 namespace {
@@ -657,9 +672,8 @@ int scan_u32(phj_ctx* c, uint32_t* data, uint32_t len, uint32_t narrays, uint32_
 // (-DPHJ_P1_PROF=1, scripts/ab_lib.sh) runs S's pass in the phase-clock form.
 template <int HK, int DPT>
 const void* pipe1024(int kpf, bool hot = false) {
-    if constexpr (DPT == 1 && PHJ_PREAGG != 0) {   // the HOT forms (phj_hot.h): S's counts weights, R's resolves them
-        if (hot && kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 2>);
-        if (hot) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 1>);
+    if constexpr (DPT == 1 && PHJ_PREAGG != 0) {   // the HOT form (phj_hot.h): S's pass counts the hot codes' weights
+        if (hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 1>);
     }
     if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, false, 1>);
     return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, PHJ_P1_PROF != 0, 2>);
@@ -719,8 +733,8 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
             const uint32_t per = (ntiles + a.nshards - 1) / a.nshards;
             const bool pipe = a.keys_only && c->tune.p1_pipe && BLOCK == 512 && ITEMS == 8;
             const bool is_r = prefix.rfind("R.", 0) == 0;
-            const bool hot = a.hot_code != nullptr;   // (the host offers it only where the 1024 x 4, one-digit-per-thread form runs)
-            const size_t lds = pipe ? chunk_pipe_lds_bytes(T, a.nbins) + chunk_pipe_hot_lds_bytes(a.nbins, hot ? (is_r ? 2 : 1) : 0)
+            const bool hot = a.hot_code != nullptr;   // S's pass only (the host offers it only where the 1024 x 4, one-digit-per-thread form runs)
+            const size_t lds = pipe ? chunk_pipe_lds_bytes(T, a.nbins) + chunk_pipe_hot_lds_bytes(a.nbins, hot ? 1 : 0)
                                : a.keys_only ? chunk_codes_lds_bytes(T, a.nbins) : sc_lds;
             const void* kfn = nullptr;
             int kblock = BLOCK;
@@ -781,6 +795,9 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                 slots = std::max<uint32_t>(
                     1, std::min<uint32_t>(per, std::min<uint32_t>(fit * 2, static_cast<uint32_t>(c->tune.p1_wpc2)) *
                                                    c->num_cus / (2 * a.nshards)));
+            // (R's pass beside the hot-key prologue: CUs left to the prologue's workgroups)
+            if (c->p1_free_cus > 0 && c->num_cus / a.nshards > c->p1_free_cus)
+                slots = std::min<uint32_t>(slots, c->num_cus / a.nshards - c->p1_free_cus);
             if (c->tune.p1_slots > 0) slots = std::min<uint32_t>(per, c->tune.p1_slots);
             if (c->tune.p1_slots < 0) slots = per;   // one tile per workgroup
             PassArgs ak = a;
@@ -1029,15 +1046,14 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
         S.chunk_check = n > 0;
     }
     unsigned long long* kept = nullptr;   // S's pre-aggregating pass: the tuples it wrote
-    if (c->hot_on) {   // phj_join's counting LDS join, default schedule (hot_begin)
+    if (c->hot_on && &S == &c->side[PHJ_SIDE_PROBE]) {   // phj_join's counting LDS join, default schedule (hot_begin): S's pass
         if (!S.hcoded) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs the chunked code pass");
         uint32_t* st = static_cast<uint32_t*>(c->hot.p);
         a.hot_code = reinterpret_cast<const unsigned long long*>(st + kHotCounters);
         a.hot_w = reinterpret_cast<unsigned long long*>(st + kHotCounters) + static_cast<size_t>(pl.nb1) * kHotPer;
         a.hot_ctl = reinterpret_cast<const uint32_t*>(a.hot_w + static_cast<size_t>(pl.nb1) * kHotPer);
         a.hot_min_mass = c->hot_min_mass;
-        a.hot_count = static_cast<unsigned long long*>(c->count.p);
-        if (&S == &c->side[PHJ_SIDE_PROBE]) kept = reinterpret_cast<unsigned long long*>(const_cast<uint32_t*>(a.hot_ctl) + 2);
+        kept = reinterpret_cast<unsigned long long*>(const_cast<uint32_t*>(a.hot_ctl) + 2);
     }
     uint32_t* tb2 = pl.npass == 2 ? static_cast<uint32_t*>(S.tbase2.p) : nullptr;
     PHJ_TRY(launch_pass(c, pl.hk, true, p1_aos, a, nt1, std::string(tag) + ".p1", n, nt1 * pl.nb1));
@@ -1135,11 +1151,11 @@ int partition_side(phj_ctx* c, int s, const Plan& pl, bool p1_only = false, unsi
 }
 
 // Hot-key pre-aggregation (phj_hot.h) for phj_join's counting LDS join in its
-// default schedule (R's chain in tile mode after S's pass on the main stream):
-// whether this join takes it. A host-side decision: both code passes must be
-// the 1024 x 4 pipelined form with one digit per thread (the LDS holds the
-// table beside the pass's own 90 KB up to 1024 clusters), R's pass must be the
-// one that resolves the weights, and S must be large enough that the sample
+// default schedule (PHJ_R_ORDER=1, R in tile mode): whether this join takes
+// it. A host-side decision: both code passes must be the 1024 x 4 pipelined
+// form with one digit per thread (the LDS holds the table beside S's pass's
+// own 90 KB up to 1024 clusters), R's tile list must be the one k_hot_resolve
+// scans, and S must be large enough that the sample
 // (kHotTiles tiles, two reads) is small against its pass: 32 times the sample.
 constexpr uint64_t kHotMinS = 32ull * kHotTiles * kHotTile;   // 16.8M tuples
 bool hot_wanted(const phj_ctx* c, const Plan& cpl, uint64_t nS, uint64_t nR) {
@@ -1152,8 +1168,8 @@ bool hot_wanted(const phj_ctx* c, const Plan& cpl, uint64_t nS, uint64_t nR) {
     return c->hot_mode == 2 || nS >= kHotMinS;
 }
 
-// The sample and the selection, on the main stream before S's pass 1; the
-// code passes of this join then take their HOT forms (c->hot_on). Forced
+// The sample and the selection, on the main stream before S's pass 1; S's
+// code pass of this join then takes its HOT form (c->hot_on). Forced
 // mode (phj_debug_preagg) takes the lowest threshold and any coverage.
 int hot_begin(phj_ctx* c, const Plan& cpl, const SideState& S) {
     PHJ_TRY(ensure(c, c->hot, hot_state_bytes(cpl.nb1)));
@@ -1171,32 +1187,56 @@ int hot_begin(phj_ctx* c, const Plan& cpl, const SideState& S) {
     h.code = reinterpret_cast<unsigned long long*>(h.counters + kHotCounters);
     h.w = h.code + static_cast<size_t>(cpl.nb1) * kHotPer;
     h.ctl = reinterpret_cast<uint32_t*>(h.w + static_cast<size_t>(cpl.nb1) * kHotPer);
-    // a table covering under an eighth of the sample is ignored by both passes
+    h.rep = reinterpret_cast<unsigned long long*>(h.ctl + kHotCtlWords);
+    // a table covering under an eighth of the sample is ignored by S's pass and k_hot_resolve
     c->hot_min_mass = forced ? 0u : static_cast<uint32_t>(std::min<uint64_t>(S.n, static_cast<uint64_t>(h.nsamp) * kHotTile) / 8);
     c->hot_n = S.n;
     // no timer events under PHJ_LEAN_TIMERS (each one between two kernels costs ~4 us)
     const bool timed = !c->lean_timers;
     if (timed) PHJ_TRY(timer_begin(c, "S.hot", 2ull * h.nsamp * kHotTile * 16));
     const void* ksample = with_hash(cpl.hk, [](auto hh) { return reinterpret_cast<const void*>(&k_hot_sample<decltype(hh)::value>); });
-    const void* kselect = with_hash(cpl.hk, [](auto hh) { return reinterpret_cast<const void*>(&k_hot_select<decltype(hh)::value>); });
     // auto mode: a first look at an eighth of the sample's tiles; without skew there the rest returns at once
     h.staged = !forced && h.nsamp == kHotTiles ? 1u : 0u;
     hipLaunchKernelGGL(k_hot_clear, dim3(16), dim3(kHotBlock), 0, c->ks, h);
     PHJ_LAUNCHED(c, "k_hot_clear");
     uint32_t phase = h.staged ? 1u : 0u;
     void* sargs[] = {&h, &phase};
-    const uint32_t first = h.staged ? (h.nsamp + kHotStage - 1) / kHotStage : h.nsamp;
-    PHJ_TRY(launch_kernel(c, ksample, dim3(first), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
+    const uint32_t first = (h.nsamp + kHotStage - 1) / kHotStage;
+    // (kHotTilesPerWg sample tiles per workgroup, one workgroup of selection:
+    // at most 32 workgroups at a time, so R's pass 1 can run beside them)
+    const uint32_t wide = (h.nsamp + kHotTilesPerWg - 1) / kHotTilesPerWg;
+    PHJ_TRY(launch_kernel(c, ksample, dim3(h.staged ? first : wide), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
     if (h.staged) {
         phase = 2;
-        PHJ_TRY(launch_kernel(c, ksample, dim3(h.nsamp), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
+        PHJ_TRY(launch_kernel(c, ksample, dim3(wide), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
     }
-    void* kargs[] = {&h};
-    PHJ_TRY(launch_kernel(c, kselect, dim3(h.nsamp), dim3(kHotBlock), kargs, 0, "k_hot_select"));
+    hipLaunchKernelGGL(k_hot_select, dim3(1), dim3(kHotBlock), hot_select_lds_bytes(cpl.nb1), c->ks, h);
+    PHJ_LAUNCHED(c, "k_hot_select");
     if (timed) PHJ_TRY(timer_end(c));
     c->hot_on = true;
     c->hot_ran = true;
     return PHJ_OK;
+}
+
+// The hot weights of the entries R holds, added to the count (k_hot_resolve):
+// on the main stream after S's pass-1 bookkeeping (which clears the count) and
+// after R's chain (RT: R's chunked code pass, its tile list).
+int hot_resolve(phj_ctx* c, const Plan& cpl, const SideState& RT) {
+    HotResolveArgs a{};
+    const uint32_t* st = static_cast<const uint32_t*>(c->hot.p);
+    a.code = reinterpret_cast<const unsigned long long*>(st + kHotCounters);
+    a.w = a.code + static_cast<size_t>(cpl.nb1) * kHotPer;
+    a.ctl = reinterpret_cast<const uint32_t*>(a.w + static_cast<size_t>(cpl.nb1) * kHotPer);
+    a.min_mass = c->hot_min_mass;
+    a.rt_base = RT.p2.tile_base;
+    a.rt_start = RT.p2.tile_start;
+    a.rt_cnt = RT.p2.tile_cnt;
+    a.r_pool = RT.p2.in_keys;
+    a.count = static_cast<unsigned long long*>(c->count.p);
+    PHJ_TRY(timer_begin(c, "R.hot", RT.n * 8));   // (an R timer: none under PHJ_LEAN_TIMERS)
+    hipLaunchKernelGGL(k_hot_resolve, dim3(cpl.nb1), dim3(kHotResolveBlock), 0, c->ks, a);
+    PHJ_LAUNCHED(c, "k_hot_resolve");
+    return timer_end(c);
 }
 
 // Build over `nseg` partitioned build segments and probe the ctx's partitioned
@@ -2848,6 +2888,8 @@ void phj_ctx_destroy(phj_ctx* c) {
                       &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->cl_done, &c->hot})
         free_buf(*b);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {c->hot_fork, c->hot_join})
+        if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     (void)hipStreamDestroy(c->aux);
     delete c;
@@ -3147,14 +3189,24 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         // after S's pass (PHJ_R_ORDER=1, default) R's chain runs on the main
         // stream itself: nothing runs beside it, and a cross-stream event wait
         // before the probe costs ~15 us (measured gap, r05z timeline)
+        // with the hot-key pre-aggregation (phj_hot.h, PHJ_HOT_EARLY_R): R's
+        // chain on the aux stream from the join's start, beside the hot-key
+        // prologue (a few narrow kernels bound by atomics), its pass 1 leaving
+        // the prologue PHJ_HOT_FREE_CUS CUs per shard; the main stream waits
+        // for it before k_hot_resolve. R's chain reads nothing of S's: the
+        // weights are resolved by k_hot_resolve, not by R's pass
+        const bool hot = hot_wanted(c, cpl, S.n, R.n);
+        const bool early_r = PHJ_HOT_EARLY_R != 0 && hot && R.n > 0;
         auto r_chain = [&](hipEvent_t after) -> int {
-            if (!r_main) {
+            if (!r_main || early_r) {
                 PHJ_HIP(c, hipStreamWaitEvent(c->aux, after, 0));
                 c->ks = c->aux;
             }
             int rc = PHJ_OK;
             if (c->tune.r_chunk && R.n > 0) {
+                c->p1_free_cus = early_r ? PHJ_HOT_FREE_CUS : 0;
                 rc = partition_state(c, R, "R", cpl, true, nullptr, 8);
+                c->p1_free_cus = 0;
                 if (rc == PHJ_OK && R.hcoded) RT = &R;
             }
             if (!RT) {
@@ -3183,21 +3235,40 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         // the code pass's bookkeeping kernel clears the count pair (an empty
         // S takes no chunked pass: a memset). R's chain after S's pass on the
         // same stream: S's bookkeeping kernel also clears R's chunk state (one
-        // memset launch and its gap fewer before R's pass)
-        const bool pre_clear = r_main && c->tune.r_chunk && R.n > 0 && !c->dry;
+        // memset launch and its gap fewer before R's pass; not with R's chain
+        // ahead of S's pass: its state is in use by then, cleared by a memset
+        // on the aux stream ahead of R's pass)
+        const bool pre_clear = r_main && !early_r && c->tune.r_chunk && R.n > 0 && !c->dry;
         if (pre_clear) {
             PHJ_TRY(ensure(c, R.ccur, chunk_state_bytes(cpl.nb1)));
             c->p1_clear = R.ccur.p;
             c->p1_clear_bytes = chunk_state_bytes(cpl.nb1);
         }
+        if (early_r) {
+            // the fork, before the prologue: the previous join's probe and
+            // k_hot_resolve read R's pool and tile list
+            for (hipEvent_t* e : {&c->hot_fork, &c->hot_join})
+                if (!*e && !(*e = new_event())) return set_err(c, PHJ_ERR_HIP, "hipEventCreate failed");
+            PHJ_HIP(c, hipEventRecord(c->hot_fork, c->stream));
+        }
         // hot probe keys (phj_hot.h): sampled and selected here; S's pass then
-        // counts them instead of writing them, R's pass adds their weights to
-        // the count (after S's bookkeeping kernel has cleared it: one stream)
+        // counts them instead of writing them, k_hot_resolve adds the weights
+        // of those R holds to the count (after S's bookkeeping kernel has
+        // cleared it: one stream)
         struct HotScope {
             phj_ctx* c;
             ~HotScope() { c->hot_on = false; }
         } hot_scope{c};
-        if (hot_wanted(c, cpl, S.n, R.n)) PHJ_TRY(hot_begin(c, cpl, S));
+        if (hot) PHJ_TRY(hot_begin(c, cpl, S));
+        if (early_r) {
+            // issued after the prologue's launches (the main stream is the
+            // step's critical path: each launch is a few us of host time) and
+            // ahead of S's pass, which is not held back by it: the workgroups
+            // of S's pass whose CUs R still holds start when R's pass ends
+            int rc = r_chain(c->hot_fork);
+            if (rc == PHJ_OK && hipEventRecord(c->hot_join, c->aux) != hipSuccess) rc = set_err(c, PHJ_ERR_HIP, "hipEventRecord failed");
+            PHJ_TRY(rc);
+        }
         const int prc = partition_side(c, PHJ_SIDE_PROBE, cpl, true, static_cast<unsigned long long*>(c->count.p));
         c->p1_clear = nullptr;
         if (prc != PHJ_OK) {
@@ -3205,12 +3276,17 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
             return prc;
         }
         if (!S.hcoded) PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 32, c->stream));
-        if (order != 2) {
+        if (order != 2 && !early_r) {
             const int rc = r_chain(t0);
             c->p1_cleared = nullptr;   // (R's pass may not have taken the chunked form)
             PHJ_TRY(rc);
         }
         if (!r_main) PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
+        if (early_r) PHJ_HIP(c, hipStreamWaitEvent(c->stream, c->hot_join, 0));
+        if (c->hot_on && R.n > 0) {
+            if (!RT) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs R's chunked code pass");
+            PHJ_TRY(hot_resolve(c, cpl, *RT));
+        }
         PHJ_TRY(phase_mark(&t1));
         // one launch, reported as "build" (the workgroups' table builds in LDS:
         // R's codes read) and "probe" (S's codes read), split by the kernel's own clocks

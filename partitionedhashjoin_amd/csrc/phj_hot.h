@@ -5,32 +5,45 @@
 // keys, though the count only needs "how many S tuples carry the key" times
 // "is it in R". So before S's pass 1 a strided sample of S is hashed and
 // counted, and the codes sampled often enough enter a hot table; S's pass then
-// counts a hot code into its entry's weight instead of writing it, and R's
-// pass adds the weight of every hot code it meets to the join's count
-// (k_chunk_codes_pipe HOT 1 / 2, phj_partition.h). A code that found no way
-// takes the normal path, so any selection is exact.
+// counts a hot code into its entry's weight instead of writing it
+// (k_chunk_codes_pipe HOT 1, phj_partition.h), and after S's pass
+// k_hot_resolve scans R's codes cluster by cluster and adds the weight of
+// every entry it meets to the join's count. R's pass 1 itself has no part in
+// it, so R's chain needs nothing of S's. A code that found no way takes the
+// normal path, so any selection is exact.
 //
 // The table: per cluster digit of pass 1, kHotSub sets (the code's top bit)
 // of kHotWays 64-bit codes, so a lookup needs only what the pass has computed
 // and reads one 16-B set; a 64-bit weight per entry; two control words
 // {entries, sampled keys covered}.
+// The prologue is narrow (at most kHotTiles / kHotTilesPerWg = 32 workgroups
+// at a time) so that it can share the chip with R's pass 1: the sample counts
+// kHotTilesPerWg tiles per workgroup in LDS and flushes once; every sampled
+// lane also leaves its code in its counter's word of a representative array
+// (plain stores, the last writer wins), and one workgroup (k_hot_select)
+// reads the counters, takes the representative of every counter at or above
+// the threshold and builds the table in LDS. The representative may be a cold
+// code that shares a hot code's counter: the hot code is then not entered.
 // Inputs without skew pay for none of this beyond a first look: in auto mode
 // a first stage counts an eighth of the sample's tiles in LDS only (no global
 // atomics: ~10 ns each per workgroup, the sample's whole cost) and adds up,
 // per tile, the keys of counters that stand out inside that one tile; unless
-// they cover a sixteenth of the stage's keys, the sample proper and the
-// selection return at once (the table stays empty, the passes skip their lookups).
+// they cover a sixteenth of the stage's keys, the sample proper returns at once
+// and the selection writes an empty table (the pass skips its lookups).
 // An empty way holds a code of another cluster (0, or E of cluster 0: no key
-// value is reserved). All of it, and the sample's counters, is written by
-// k_hot_clear in every join: nothing is kept from the join before.
+// value is reserved). The counters and control words are cleared by
+// k_hot_clear and the table is written by k_hot_select in every join; the
+// representatives are not cleared (a counter that counts in this join was
+// written in this join): nothing is kept from the join before.
 #pragma once
 
 #include "phj_partition.h"
 
 namespace phj {
 
-constexpr uint32_t kHotTile = 4096;        // keys of one sample tile (one workgroup of k_hot_sample)
+constexpr uint32_t kHotTile = 4096;        // keys of one sample tile
 constexpr uint32_t kHotTiles = 128;        // sample tiles, spread evenly over S
+constexpr uint32_t kHotTilesPerWg = 4;     // sample tiles of one workgroup of k_hot_sample (phases 0 and 2)
 constexpr uint32_t kHotCounters = 65536;   // sample counters (L2-resident, 256 KB), 16 bits each in the workgroups' LDS
 constexpr uint32_t kHotThreshold = 16;     // sample count of a hot code at kHotTiles tiles (3.1e-5 of S)
 constexpr uint32_t kHotHeavy = 8;          // codes sampled this many thresholds over are entered first
@@ -38,6 +51,15 @@ constexpr uint32_t kHotBlock = 1024;
 constexpr uint32_t kHotStage = 8;          // auto mode: every 8th sample tile is the first stage
 constexpr uint32_t kHotStageCount = 4;     // ... a tile's counter stands out at this count (4 of 4096 keys; uniform keys: none does)
 constexpr uint32_t kHotCtlGo = 4, kHotCtlDone = 5, kHotCtlStage = 6, kHotCtlWords = 8;   // hot_ctl beyond kHotCtl*: 2-3 = the tuples S's pass wrote
+constexpr uint32_t kHotListHeavy = 4096, kHotListRest = 12288;   // k_hot_select's LDS lists of counters at or above the threshold
+constexpr uint32_t kHotResolveBlock = 1024;   // k_hot_resolve: a wave per tile of R's tile list
+
+// dynamic LDS of k_hot_select
+__host__ __device__ constexpr size_t hot_select_lds_bytes(uint32_t nb) {
+    return static_cast<size_t>(nb) * kHotPer * 8 + static_cast<size_t>(kHotListHeavy + kHotListRest) * 4;
+}
+static_assert(kHotTilesPerWg * kHotTile <= 65535, "k_hot_sample: the 16-bit halves of an LDS word must not carry");
+static_assert(kHotCounters % (4 * kHotBlock) == 0, "k_hot_select: whole 16-B loads of counters per thread");
 
 struct HotArgs {
     const int64_t* rel;     // S: {id, payload} pairs
@@ -51,12 +73,14 @@ struct HotArgs {
     unsigned long long* code;   // [nb][kHotPer]
     unsigned long long* w;      // [nb][kHotPer]
     uint32_t* ctl;          // kHotCtl*
-    uint32_t staged;        // 1: two sample stages (k_hot_sample phase 1, 2), else one (phase 0) and the selection always runs
+    unsigned long long* rep;    // [kHotCounters] a code that counted into the counter in this join
+    uint32_t staged;        // 1: two sample stages (k_hot_sample phase 1, 2), else one (phase 0)
 };
 
-// device words of the state: counters, codes, weights, control words
+// device words of the state: counters, codes, weights, control words, representatives
 __host__ __device__ constexpr size_t hot_state_bytes(uint32_t nb) {
-    return static_cast<size_t>(kHotCounters) * 4 + static_cast<size_t>(nb) * kHotPer * 16 + kHotCtlWords * 4;
+    return static_cast<size_t>(kHotCounters) * 4 + static_cast<size_t>(nb) * kHotPer * 16 + kHotCtlWords * 4 +
+           static_cast<size_t>(kHotCounters) * 8;
 }
 
 __device__ __forceinline__ uint32_t hot_counter_of(uint64_t code) {
@@ -71,36 +95,47 @@ __device__ __forceinline__ uint32_t hot_tile_of(const HotArgs& a, uint32_t i) {
 __global__ __launch_bounds__(kHotBlock) void k_hot_clear(HotArgs a) {
     const uint32_t i0 = blockIdx.x * kHotBlock + threadIdx.x, step = gridDim.x * kHotBlock;
     for (uint32_t i = i0; i < kHotCounters; i += step) a.counters[i] = 0;
-    for (uint32_t i = i0; i < a.nb * kHotPer; i += step) {
-        a.code[i] = i < kHotPer ? a.e0 : 0ull;
-        a.w[i] = 0;
-    }
     if (i0 < kHotCtlWords) a.ctl[i0] = i0 == kHotCtlGo && !a.staged ? 1u : 0u;
 }
 
-// One workgroup per sample tile: its keys' codes counted in LDS (two 16-bit
-// counters per word: a tile has 4096 keys, so no half carries), then the
-// non-zero counters added to the global ones.
-// phase 0: every sample tile; 1: the first look at tiles 0, 8, 16, .. (nothing
-// global but the verdict); 2: every sample tile, if phase 1 said go
+// Sample tiles counted in LDS (two 16-bit counters per word: a workgroup
+// counts at most kHotTilesPerWg * 4096 keys, so no half carries), then the
+// non-zero counters added to the global ones: the flush is the same number of
+// atomic instructions however many tiles were counted.
+// phase 0: every sample tile, kHotTilesPerWg per workgroup; 1: the first look
+// at tiles 0, 8, 16, .. , one per workgroup (nothing global but the verdict);
+// 2: as 0, if phase 1 said go
 template <int HK>
 __global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a, uint32_t phase) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hot_lds[];   // [kHotCounters / 2]
     const uint32_t tid = threadIdx.x;
     if (phase == 2 && __hip_atomic_load(&a.ctl[kHotCtlGo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;   // workgroup-uniform
     const uint32_t b = blockIdx.x;
-    const uint32_t si = phase == 1 ? b * kHotStage : b;
-    if (si >= a.nsamp) return;
+    const uint32_t s0 = phase == 1 ? b * kHotStage : b * kHotTilesPerWg;
+    const uint32_t s1 = phase == 1 ? s0 + 1 : min(s0 + kHotTilesPerWg, a.nsamp);
+    if (s0 >= a.nsamp) return;
     for (uint32_t i = tid; i < kHotCounters / 2; i += kHotBlock) hot_lds[i] = 0;
     __syncthreads();
-    const uint32_t lo = hot_tile_of(a, si) * kHotTile;
     const longlong2* rel = reinterpret_cast<const longlong2*>(a.rel);
+    // every key of the workgroup's tiles requested before the first is used
+    constexpr uint32_t I = kHotTile / kHotBlock, K = kHotTilesPerWg * I;
+    int64_t key[K];
+    uint32_t have = 0;
 #pragma unroll
-    for (uint32_t i = 0; i < kHotTile / kHotBlock; i++) {
-        const uint32_t ix = lo + i * kHotBlock + tid;
-        if (ix >= a.n) continue;
-        const uint32_t ci = hot_counter_of(hash64<HK>(static_cast<uint64_t>(rel[ix].x), a.f.seed));
+    for (uint32_t k = 0; k < K; k++) {
+        const uint32_t si = s0 + k / I;
+        const uint32_t ix = hot_tile_of(a, si < s1 ? si : s0) * kHotTile + (k % I) * kHotBlock + tid;
+        const bool ok = si < s1 && ix < a.n;
+        key[k] = rel[ok ? ix : 0].x;
+        have |= (ok ? 1u : 0u) << k;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < K; k++) {
+        if (!((have >> k) & 1u)) continue;
+        const uint64_t code = hash64<HK>(static_cast<uint64_t>(key[k]), a.f.seed);
+        const uint32_t ci = hot_counter_of(code);
         atomicAdd(&hot_lds[ci >> 1], 1u << ((ci & 1u) * 16));
+        if (phase != 1) a.rep[ci] = code;
     }
     __syncthreads();
     if (phase != 1) {
@@ -137,69 +172,167 @@ __global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a, uint32_t ph
     }
 }
 
-// The sample again: a code whose counter reached the threshold enters a set
-// of its digit. The ways are tried in fixed order with a 64-bit
-// compare-and-swap and never change once taken, so a code sits in one way at
-// most; a set that is full drops the code. The heavy counters go first in
-// every workgroup, so an overflowing set mostly keeps the larger counts. A
-// hot code fills thousands of lanes (the hottest key of Zipf 1.05 is 7 % of
-// them), and that many atomics on one set took 0.18 ms: per workgroup only
-// the first lane of each counter (an LDS bitmap) goes to the table, so a set
-// sees at most one lane per workgroup and code. Codes that only share a hot
-// code's counter may enter too: harmless (a wasted way). The sampled keys the
-// table covers are summed once per counter, by the lane that sets the
-// counter's top bit.
-constexpr uint32_t kHotClaimed = 0x80000000u;
-template <int HK>
+// The selection, one workgroup: the counters read with coalesced loads, and
+// the representative of every counter that reached the
+// threshold enters a set of its digit in an LDS copy of the table. The ways
+// are tried in fixed order with a 64-bit LDS compare-and-swap and never change
+// once taken; a set that is full drops the code. The heavy counters go first
+// (a barrier between the rounds), so an overflowing set keeps the larger
+// counts. A counter has one representative and a code has one counter, so no
+// code is offered twice. The lists hold four times the ways of the largest
+// table; a counter past their end is dropped as a full set would drop it. Then the table, zero weights and {entries, sampled
+// keys the entries' counters cover} are written out; without a go from the
+// first look that is an empty table.
 __global__ __launch_bounds__(kHotBlock) void k_hot_select(HotArgs a) {
-    __shared__ uint32_t seen[kHotCounters / 32];   // counters a lane of this workgroup took
-    const uint32_t tid = threadIdx.x;
-    if (__hip_atomic_load(&a.ctl[kHotCtlGo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;   // workgroup-uniform
-    for (uint32_t i = tid; i < kHotCounters / 32; i += kHotBlock) seen[i] = 0;
-    const uint32_t lo = hot_tile_of(a, blockIdx.x) * kHotTile;
-    const longlong2* rel = reinterpret_cast<const longlong2*>(a.rel);
-    constexpr uint32_t I = kHotTile / kHotBlock;
-    uint64_t code[I];
-    uint32_t cnt[I], ci[I];
-#pragma unroll
-    for (uint32_t i = 0; i < I; i++) {
-        const uint32_t ix = lo + i * kHotBlock + tid;
-        code[i] = 0;
-        cnt[i] = 0;
-        ci[i] = 0;
-        if (ix >= a.n) continue;
-        code[i] = hash64<HK>(static_cast<uint64_t>(rel[ix].x), a.f.seed);
-        ci[i] = hot_counter_of(code[i]);
-        cnt[i] = a.counters[ci[i]] & ~kHotClaimed;
-    }
+    extern __shared__ __attribute__((aligned(16))) unsigned long long hot_tab[];   // [nb][kHotPer], then the lists
+    __shared__ uint32_t s_entries, s_mass, s_scan[kHotBlock / 64];
+    const uint32_t tid = threadIdx.x, slots = a.nb * kHotPer;
+    uint32_t* hot_list = reinterpret_cast<uint32_t*>(hot_tab + slots);   // [kHotListHeavy + kHotListRest]
+    for (uint32_t i = tid; i < slots; i += kHotBlock) hot_tab[i] = i < kHotPer ? a.e0 : 0ull;
+    if (tid == 0) s_entries = s_mass = 0;
     __syncthreads();
-    const uint32_t heavy = a.thr * kHotHeavy;
-    uint32_t mass = 0;
-    for (int round = 0; round < 2; round++) {
+    if (__hip_atomic_load(&a.ctl[kHotCtlGo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {   // workgroup-uniform
+        // the counters that reached the threshold, compacted into two LDS
+        // lists (heavy, the rest: a scan of the threads' numbers of each), so
+        // that the rounds below share them evenly: {counter, count} in 16
+        // bits each (a count that does not fit is read again)
+        constexpr uint32_t V = kHotCounters / (4 * kHotBlock);
+        const uint32_t heavy = a.thr * kHotHeavy;
+        uint4 cnt[V];
 #pragma unroll
-        for (uint32_t i = 0; i < I; i++) {
-            const bool mine = round == 0 ? cnt[i] >= heavy : cnt[i] >= a.thr && cnt[i] < heavy;
-            if (!mine) continue;
-            const uint32_t bit = 1u << (ci[i] & 31u);
-            if (atomicOr(&seen[ci[i] >> 5], bit) & bit) continue;   // another lane of the workgroup has this counter
-            const uint32_t d = static_cast<uint32_t>(q_from_hash(code[i], a.f) >> a.f.shift) & a.f.dmask;
-            if (d >= a.nb) continue;
-            const unsigned long long empty = d == 0 ? a.e0 : 0ull;
-            unsigned long long* set = a.code + static_cast<size_t>(d) * kHotPer + (code[i] >> 63) * kHotWays;
-            for (uint32_t w = 0; w < kHotWays; w++) {
-                unsigned long long v = __hip_atomic_load(&set[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (v == empty) v = atomicCAS(&set[w], empty, static_cast<unsigned long long>(code[i]));
-                else if (v != code[i]) continue;
-                if (v == empty) atomicAdd(&a.ctl[kHotCtlEntries], 1u);   // this lane entered it
-                if (v == empty || v == code[i]) {
-                    if (!(atomicOr(&a.counters[ci[i]], kHotClaimed) & kHotClaimed)) mass += cnt[i];
-                    break;
+        for (uint32_t j = 0; j < V; j++) cnt[j] = reinterpret_cast<const uint4*>(a.counters)[j * kHotBlock + tid];
+        uint32_t at[2] = {0, 0};
+#pragma unroll
+        for (uint32_t j = 0; j < V; j++) {
+            const uint32_t c4[4] = {cnt[j].x, cnt[j].y, cnt[j].z, cnt[j].w};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                at[0] += c4[k] >= heavy ? 1u : 0u;
+                at[1] += c4[k] >= a.thr && c4[k] < heavy ? 1u : 0u;
+            }
+        }
+        uint32_t total[2];
+        at[0] = block_exclusive_scan_t<kHotBlock / 64>(at[0], s_scan, total[0]);
+        at[1] = block_exclusive_scan_t<kHotBlock / 64>(at[1], s_scan, total[1]);
+#pragma unroll
+        for (uint32_t j = 0; j < V; j++) {
+            const uint32_t c4[4] = {cnt[j].x, cnt[j].y, cnt[j].z, cnt[j].w};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t n = c4[k], item = ((j * kHotBlock + tid) * 4 + k) | (min(n, 0xffffu) << 16);
+                if (n >= heavy) {
+                    if (at[0] < kHotListHeavy) hot_list[at[0]] = item;
+                    at[0]++;
+                } else if (n >= a.thr) {
+                    if (at[1] < kHotListRest) hot_list[kHotListHeavy + at[1]] = item;
+                    at[1]++;
                 }
             }
         }
         __syncthreads();
+        uint32_t entries = 0, mass = 0;
+        for (int round = 0; round < 2; round++) {
+            const uint32_t base = round == 0 ? 0u : kHotListHeavy;
+            const uint32_t len = min(total[round], round == 0 ? kHotListHeavy : kHotListRest);
+            for (uint32_t i = tid; i < len; i += kHotBlock) {
+                const uint32_t item = hot_list[base + i], ci = item & 0xffffu;
+                const uint32_t n = (item >> 16) == 0xffffu ? a.counters[ci] : item >> 16;
+                const unsigned long long code = a.rep[ci];
+                const uint32_t d = static_cast<uint32_t>(q_from_hash(code, a.f) >> a.f.shift) & a.f.dmask;
+                if (d >= a.nb) continue;
+                const unsigned long long empty = d == 0 ? a.e0 : 0ull;
+                unsigned long long* set = hot_tab + static_cast<size_t>(d) * kHotPer + (code >> 63) * kHotWays;
+                for (uint32_t w = 0; w < kHotWays; w++) {
+                    const unsigned long long v = atomicCAS(&set[w], empty, code);
+                    if (v == empty) entries++;   // this lane entered it
+                    if (v == empty || v == code) {
+                        mass += n;
+                        break;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (entries) atomicAdd(&s_entries, entries);
+        if (mass) atomicAdd(&s_mass, mass);
+        __syncthreads();
     }
-    if (mass) atomicAdd(&a.ctl[kHotCtlMass], mass);
+    for (uint32_t i = tid; i < slots; i += kHotBlock) {
+        a.code[i] = hot_tab[i];
+        a.w[i] = 0;
+    }
+    if (tid == 0) {
+        a.ctl[kHotCtlEntries] = s_entries;
+        a.ctl[kHotCtlMass] = s_mass;
+    }
+}
+
+// The hot weights resolved against R, after S's pass 1 and its bookkeeping
+// (which clears the count) and after R's pass-1 tile list is built: one
+// workgroup per cluster reads the cluster's entries, returns at once when the
+// table is ignored (the pass's own test) or the cluster's weights are all 0,
+// else scans the cluster's R codes tile by tile through R's pass-1 tile list
+// (any number of tiles and codes: the HBM-table clusters need no case of
+// their own), flags the entries it meets and adds each flagged entry's weight
+// once: a key R holds twice counts once, as in the probe's set test.
+struct HotResolveArgs {
+    const unsigned long long* code;   // [nb][kHotPer]
+    const unsigned long long* w;      // [nb][kHotPer]
+    const uint32_t* ctl;
+    uint32_t min_mass;
+    const uint32_t* rt_base;          // [nb + 1]: R's pass-1 tiles of each cluster
+    const uint32_t* rt_start;         // tile -> first pool slot
+    const uint32_t* rt_cnt;           // tile -> codes
+    const int64_t* r_pool;            // R's chunk pool (codes)
+    unsigned long long* count;
+};
+
+__global__ __launch_bounds__(kHotResolveBlock) void k_hot_resolve(HotResolveArgs a) {
+    __shared__ uint32_t met[kHotPer];
+    const uint32_t d = blockIdx.x, tid = threadIdx.x;
+    if (a.ctl[kHotCtlEntries] == 0 || a.ctl[kHotCtlMass] < a.min_mass) return;   // grid-uniform
+    unsigned long long hc[kHotPer], hw[kHotPer];
+    bool any = false;
+#pragma unroll
+    for (uint32_t e = 0; e < kHotPer; e++) {
+        hc[e] = a.code[static_cast<size_t>(d) * kHotPer + e];
+        hw[e] = a.w[static_cast<size_t>(d) * kHotPer + e];
+        any = any || hw[e] != 0;
+    }
+    if (!any) return;   // workgroup-uniform
+    if (tid < kHotPer) met[tid] = 0;
+    __syncthreads();
+    // a wave per tile (R's pass has 8 shards: most of a cluster's tiles are
+    // partial, a shard's share of its codes), U loads of a lane in flight
+    constexpr uint32_t NW = kHotResolveBlock / 64, U = 8;
+    const uint32_t wave = tid / 64, l = tid % 64;
+    const uint32_t t0 = a.rt_base[d], t1 = a.rt_base[d + 1];
+    for (uint32_t ti = t0 + wave; ti < t1; ti += NW) {
+        const int64_t* src = a.r_pool + a.rt_start[ti];
+        const uint32_t c = a.rt_cnt[ti];
+        for (uint32_t r0 = 0; r0 < c; r0 += U * 64) {
+            unsigned long long v[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                const uint32_t r = r0 + u * 64 + l;
+                v[u] = static_cast<unsigned long long>(src[r < c ? r : 0]);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                if (r0 + u * 64 + l >= c) continue;
+#pragma unroll
+                for (uint32_t e = 0; e < kHotPer; e++)
+                    if (v[u] == hc[e] && hw[e] != 0) met[e] = 1;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long sum = 0;
+#pragma unroll
+        for (uint32_t e = 0; e < kHotPer; e++) sum += met[e] ? hw[e] : 0ull;
+        if (sum) atomicAdd(a.count, sum);
+    }
 }
 
 }  // namespace phj

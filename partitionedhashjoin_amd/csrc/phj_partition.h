@@ -141,8 +141,8 @@ struct PassArgs {
     unsigned long long* prof;   // k_chunk_codes_pipe PROF: clocks of its phases, kP1ProfWords (diagnostics)
     // k_chunk_codes_pipe HOT (phj_hot.h): the hot table of this join's probe
     // side, [nbins][kHotPer] codes and 64-bit weights, its control words
-    // (kHotCtl*), the sample mass below which the table is ignored, and (R's
-    // pass) the join's count word
+    // (kHotCtl*), the sample mass below which the table is ignored
+    // (hot_count: no pass reads it; k_hot_resolve adds the weights to the count)
     const unsigned long long* hot_code;
     unsigned long long* hot_w;
     const uint32_t* hot_ctl;
@@ -1127,10 +1127,10 @@ __device__ __forceinline__ unsigned long long pipe_hint(uint32_t j, uint32_t rid
 __host__ __device__ constexpr size_t chunk_pipe_lds_bytes(int T, uint32_t nb) {
     return 2 * static_cast<size_t>(T) * 8 + (static_cast<size_t>(2 * nb + 3) / 4 * 4 + 4 * static_cast<size_t>(nb)) * 4 + 128;
 }
-// ... and after them the HOT forms' copy of the hot table: the codes, and
-// (HOT 1) the workgroup's 32-bit weights and a word per thread (1024 of them)
+// ... and after them the HOT form's copy of the hot table: the codes, the
+// workgroup's 32-bit weights and a word per thread (1024 of them)
 __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int hot) {
-    return hot == 0 ? 0 : static_cast<size_t>(nb) * kHotPer * (hot == 1 ? 12 : 8) + (hot == 1 ? 4096 : 0);
+    return hot == 0 ? 0 : static_cast<size_t>(nb) * kHotPer * 12 + 4096;
 }
 
 // Registers: one workgroup per CU (LDS). WPE: waves per SIMD the registers
@@ -1146,18 +1146,17 @@ __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int h
 // of its digit. 1 (S's pass): a code found there adds 1 to its entry's LDS
 // weight and is neither ranked nor written, so a tile's valid count is the
 // scan's total of kept codes; the workgroup adds its weights to the global
-// ones when it ends. 2 (R's pass, after S's on the same stream): a code found
-// there takes the entry's global weight by an exchange with 0 (a key R holds
-// twice counts once, as the probe's set test) and adds it to the count; the
-// code is written as ever. A table with no entries, or covering less than
+// ones when it ends (k_hot_resolve then adds the weights of the entries R
+// holds to the count). A table with no entries, or covering less than
 // hot_min_mass sampled keys, skips the lookups (workgroup-uniform, and the
-// same in both passes: they read the same words).
+// same test as k_hot_resolve's: they read the same words).
 template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : BLOCK / 256)))
 void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     constexpr int NW = BLOCK / 64;
     constexpr int T = BLOCK * ITEMS;
     static_assert(NW <= 16, "scan words [0, NW) below the reservation words");
+    static_assert(HOT == 0 || HOT == 1, "HOT 1: S's pre-aggregating pass");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t nb = a.nbins;   // host: nb <= DPT * BLOCK
     int64_t* sbuf = reinterpret_cast<int64_t*>(smem);                       // [2][T] sorted codes
@@ -1355,9 +1354,6 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                             atomicAdd(m ? &hwt[ew] : &hown[tid], m ? 1u : 0u);
 #endif
                             keep &= ~((m ? 1u : 0u) << i);
-                        } else if (m) {
-                            const unsigned long long got = atomicExch(&a.hot_w[ew], 0ull);
-                            if (got) atomicAdd(a.hot_count, got);
                         }
                     }
                 }

@@ -4,7 +4,9 @@
 #  measurement-only compile flags: `make prof-lib` -> build/libphj_prof.so, the phase-clock
 #  forms of S's pass 1 and of the LDS join (-DPHJ_P1_PROF=1 -DPHJ_CL_PROF=1, stderr per join);
 #  `make build/libphj_res1.so HIPDEFS=-DPHJ_PIPE_RES=1`-style variants the same way; PHJ_LIB selects it;
-#  `make build/libphj_nopreagg.so HIPDEFS=-DPHJ_PREAGG=0`: without the hot-key pre-aggregation, csrc/phj_hot.h)
+#  `make build/libphj_nopreagg.so HIPDEFS=-DPHJ_PREAGG=0`: without the hot-key pre-aggregation, csrc/phj_hot.h;
+#  `make build/libphj_late.so HIPDEFS=-DPHJ_HOT_EARLY_R=0`: R's chain after S's pass 1, not beside the hot-key prologue;
+#  `HIPDEFS=-DPHJ_HOT_FREE_CUS=N`: the CUs per XCD R's pass 1 leaves to the prologue)
 # The JSON lines go to $OUT (default ab_out/).
 set -o pipefail
 OUT=${OUT:-ab_out}
