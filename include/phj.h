@@ -377,6 +377,59 @@ const phj_joined *phj_joined_rows(phj_ctx *ctx, uint64_t *n);
 /* Copy the first n rows of the last phj_join_materialize / phj_join_inner / phj_join_rows to host memory. */
 int phj_joined_download(phj_ctx *ctx, phj_joined *host, uint64_t n);
 
+/* ---- aggregates over the join, without its rows ----
+ * Replaces nothing in the reference, which only counts. What a caller usually
+ * wants of R ⋈ S is an aggregate: Σ payload over the pairs, or, per build
+ * tuple, its number of probe partners and the sum of their payloads (dimension
+ * ⋈ fact, GROUP BY dimension). One accumulating pass over the join the inner
+ * join's count pass does; nothing is stored or addressed per pair. */
+#define PHJ_AGG_GROUPS        0x1  /* also produce one phj_group_row per build tuple */
+#define PHJ_AGG_MATCHED_ONLY  0x2  /* with GROUPS: drop build tuples with no partner */
+typedef struct phj_join_totals {   /* 40 B; every sum is modulo 2^64 (two's complement wrap) */
+    uint64_t pairs;          /* |R ⋈ S| == the matches of the inner join's count */
+    uint64_t probe_matched;  /* probe tuples with >= 1 partner == the matches of the counting join */
+    int64_t  sum_a;          /* Σ over pairs of the build payload */
+    int64_t  sum_b;          /* Σ over pairs of the probe payload */
+    int64_t  sum_ab;         /* Σ over pairs of build payload * probe payload */
+} phj_join_totals;
+typedef struct phj_group_row {     /* 32 B */
+    int64_t id;
+    int64_t payload_a;             /* the build tuple */
+    uint64_t partners;             /* probe tuples with its id */
+    int64_t sum_b;                 /* Σ of their payloads, modulo 2^64 */
+} phj_group_row;
+/* The totals of R ⋈ S into *t and, with PHJ_AGG_GROUPS, the group rows.
+ *  - Synchronous; r->matches == t->pairs.
+ *  - PHJ_ALGO_RADIX (with the inner join's precondition: the fused LDS join)
+ *    and PHJ_ALGO_NO_PARTITIONING.
+ *  - Single-device contexts only: a group or rank context returns
+ *    PHJ_ERR_STATE ("single-device contexts only").
+ *  - flags with a bit above 0x2, or MATCHED_ONLY without GROUPS, give
+ *    PHJ_ERR_INVALID.
+ *  - No limit at 2^32 pairs: all five totals stay exact (the sums modulo 2^64)
+ *    whatever the pair count. The sides' own limits are those of the inner
+ *    join's count.
+ *  - Group rows live in a ctx-owned buffer of their own, valid until the next
+ *    aggregate join. The rows of an earlier materialised join stay untouched,
+ *    and a later materialised join does not disturb the group rows. One row
+ *    per build tuple, in unspecified order: |R| rows, or only those with
+ *    partners > 0 under MATCHED_ONLY. Without GROUPS the group rows are 0
+ *    after the call.
+ *  - An empty side is not an error: the totals are all zero. With GROUPS and
+ *    an empty probe side every build tuple gets a {id, payload_a, 0, 0} row
+ *    copied from the bound relation (none under MATCHED_ONLY); no join runs.
+ *  - Timers beside the partition / np.build timers: `agg.join` (the
+ *    accumulating pass) and, with GROUPS, `agg.groups` (the clear of the
+ *    accumulators and the compaction). algorithmic_bytes counts what each
+ *    pass must move (DESIGN.md §Aggregate joins). */
+int phj_join_aggregate(phj_ctx *ctx, const phj_join_params *p, uint32_t flags, phj_join_result *r,
+                       phj_join_totals *t);
+/* The group rows of the last aggregate join: device pointer (ctx-owned, valid
+ * until the next one) and count. */
+const phj_group_row *phj_group_rows(phj_ctx *ctx, uint64_t *n);
+/* Copy the first n group rows of the last aggregate join to host memory. */
+int phj_group_download(phj_ctx *ctx, phj_group_row *host, uint64_t n);
+
 /* ---- building blocks (multi-GPU: range-sharded relations, RCCL exchange) ---- */
 /* Radix-partition the bound relation of `side`; fills `out` with ctx-owned views.
  * Asynchronous on the ctx stream (order later work on the same stream). */

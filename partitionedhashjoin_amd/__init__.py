@@ -14,17 +14,18 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (ALGO_NO_PARTITIONING, ALGO_RADIX, BUILD_ANTI, BUILD_OUTER, CTX_EXCHANGE, CTX_LOCAL, FULL_OUTER,
+from ._capi import (AGG_GROUPS, AGG_MATCHED_ONLY, ALGO_NO_PARTITIONING, ALGO_RADIX, BUILD_ANTI, BUILD_OUTER, CTX_EXCHANGE, CTX_LOCAL, FULL_OUTER,
                     HASH_MURMUR3, HASH_XXH3, INNER, NULL_PAYLOAD, PATH_CODE_TABLES, PATH_LDS_JOIN,
                     PATH_NO_PARTITIONING, PATH_PARTITIONED, PROBE_ANTI, PROBE_OUTER, ROWS_BUILD_ONLY, ROWS_PAIRS,
-                    ROWS_PROBE_ONLY, SIDE_BUILD, SIDE_PROBE, JoinParams, JoinResult, Partitioned, PhjError, RowCounts)
+                    ROWS_PROBE_ONLY, SIDE_BUILD, SIDE_PROBE, GroupRow, JoinParams, JoinResult, JoinTotals, Partitioned,
+                    PhjError, RowCounts)
 
 __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_JOIN", "PATH_CODE_TABLES",
            "PATH_PARTITIONED", "PATH_NO_PARTITIONING", "count_contribution", "count_verdict", "comm_unique_id", "CTX_EXCHANGE", "CTX_LOCAL", "radix_params", "nopart_params", "JoinParams", "JoinResult",
            "Partitioned", "PhjError", "ALGO_RADIX", "ALGO_NO_PARTITIONING", "HASH_XXH3",
            "HASH_MURMUR3", "SIDE_BUILD", "SIDE_PROBE", "DEFAULT_SEED", "RowCounts", "ROWS_PAIRS", "ROWS_PROBE_ONLY",
            "ROWS_BUILD_ONLY", "INNER", "PROBE_OUTER", "BUILD_OUTER", "FULL_OUTER", "PROBE_ANTI", "BUILD_ANTI",
-           "NULL_PAYLOAD"]
+           "NULL_PAYLOAD", "JoinTotals", "GroupRow", "AGG_GROUPS", "AGG_MATCHED_ONLY"]
 
 DEFAULT_SEED = 0x9E3779B97F4A7C15
 PART_STABLE = 0x1   # include/phj.h PHJ_PART_STABLE
@@ -304,6 +305,29 @@ class Context:
         n = total.value if n is None else n
         out = np.zeros((n, 3), dtype=np.int64)
         self._check(self._L.phj_joined_download(self._h, out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def join_aggregate(self, params: JoinParams, groups: bool = False, matched_only: bool = False):
+        """phj_join_aggregate: (JoinResult, JoinTotals) of R join S without its
+        rows: pairs, probe tuples with a partner, and the sums over the pairs
+        of the build payload, the probe payload and their product (modulo
+        2^64); no limit at 2^32 pairs. groups=True also leaves one row per
+        build tuple (matched_only=True: per build tuple with a partner) for
+        groups(). r.matches == totals.pairs."""
+        flags = (AGG_GROUPS if groups else 0) | (AGG_MATCHED_ONLY if matched_only else 0)
+        r, t = JoinResult(), JoinTotals()
+        self._check(self._L.phj_join_aggregate(self._h, C.byref(params), flags, C.byref(r), C.byref(t)))
+        return r, t
+
+    def groups(self, n: int | None = None) -> np.ndarray:
+        """Group rows of the last join_aggregate as an (n, 4) int64 array
+        {id, payloadA, partners, sum of the partners' payloads}, in unspecified
+        order; the partners column is a uint64 reinterpreted as int64."""
+        total = C.c_uint64(0)
+        self._L.phj_group_rows(self._h, C.byref(total))
+        n = total.value if n is None else n
+        out = np.zeros((n, 4), dtype=np.int64)
+        self._check(self._L.phj_group_download(self._h, out.ctypes.data_as(C.c_void_p), n))
         return out
 
     def partition(self, side: int, params: JoinParams) -> Partitioned:

@@ -41,7 +41,7 @@ EXPORTED = [
     "phj_ctx_info", "phj_shard_range", "phj_probe_pass1", "phj_debug_poison_chunk_table", "phj_debug_poison_alloc", "phj_debug_fail_member", "phj_debug_exchange_block", "phj_exchange_geometry",
     "phj_exchange_layout", "phj_count_contribution", "phj_count_verdict", "phj_join_path",
     "phj_join_inner_count", "phj_join_inner", "phj_join_rows_count", "phj_join_rows",
-    "phj_debug_preagg",
+    "phj_debug_preagg", "phj_join_aggregate", "phj_group_rows", "phj_group_download",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
@@ -52,6 +52,7 @@ PATH_NO_PARTITIONING, PATH_LDS_JOIN, PATH_CODE_TABLES, PATH_PARTITIONED = 0, 1, 
 ROWS_PAIRS, ROWS_PROBE_ONLY, ROWS_BUILD_ONLY = 0x1, 0x2, 0x4
 INNER, PROBE_OUTER, BUILD_OUTER, FULL_OUTER, PROBE_ANTI, BUILD_ANTI = 1, 3, 5, 7, 2, 4
 NULL_PAYLOAD = -2**63   # the default marker for the missing side (INT64_MIN)
+AGG_GROUPS, AGG_MATCHED_ONLY = 0x1, 0x2   # phj_join_aggregate's flags
 
 
 class Tuple(C.Structure):
@@ -94,6 +95,22 @@ class RowCounts(C.Structure):
     def as_dict(self):
         return {"pairs": self.pairs, "probe_only": self.probe_only, "build_only": self.build_only,
                 "rows": self.rows}
+
+
+class JoinTotals(C.Structure):
+    """phj_join_totals: the aggregates of phj_join_aggregate over R join S
+    (every sum modulo 2^64)."""
+    _fields_ = [("pairs", C.c_uint64), ("probe_matched", C.c_uint64), ("sum_a", C.c_int64),
+                ("sum_b", C.c_int64), ("sum_ab", C.c_int64)]
+
+    def as_dict(self):
+        return {"pairs": self.pairs, "probe_matched": self.probe_matched, "sum_a": self.sum_a,
+                "sum_b": self.sum_b, "sum_ab": self.sum_ab}
+
+
+class GroupRow(C.Structure):
+    """phj_group_row: a build tuple, its probe partners and the sum of their payloads."""
+    _fields_ = [("id", C.c_int64), ("payload_a", C.c_int64), ("partners", C.c_uint64), ("sum_b", C.c_int64)]
 
 
 class Partitioned(C.Structure):
@@ -170,6 +187,10 @@ def load():
                               C.POINTER(RowCounts)]),
         "phj_joined_rows": (P, [P, C.POINTER(u64)]),
         "phj_joined_download": (i, [P, P, u64]),
+        "phj_join_aggregate": (i, [P, C.POINTER(JoinParams), C.c_uint32, C.POINTER(JoinResult),
+                                   C.POINTER(JoinTotals)]),
+        "phj_group_rows": (P, [P, C.POINTER(u64)]),
+        "phj_group_download": (i, [P, P, u64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -49,6 +49,7 @@
 #include "phj_join.h"
 #include "phj_inner.h"
 #include "phj_outer.h"
+#include "phj_agg.h"
 #include "phj_mat.h"
 #include "phj_partition.h"
 #include "phj_hot.h"
@@ -189,6 +190,8 @@ struct phj_ctx {
     DevBuf fitems, split, cl_prof;
     DevBuf mat_mark, mat_cnt, mat_rows;   // materialised join: per-probe match, block offsets, rows
     DevBuf row_hit, row_only, row_cnt;    // phj_join_rows: build hit flags, probe-only bitmap, build block offsets
+    DevBuf agg_acc, agg_cnt, agg_rows, agg_res;   // phj_join_aggregate: accumulator planes, block offsets, group rows, {5 totals, rows}
+    uint64_t agg_n = 0;   // group rows of the last phj_join_aggregate
     uint64_t mat_n = 0;   // fused join: item slots; wave clocks {build, probe} since the last timer reset
     std::vector<hipEvent_t> evpool;
     size_t evnext = 0;
@@ -2386,6 +2389,224 @@ int join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool em
     return PHJ_OK;
 }
 
+// ---- aggregates over the join (phj_agg.h): totals and groups ----
+
+// Bytes beyond partitioning / the table build (DESIGN.md §Aggregate joins).
+// The totals pass reads both columns of both sides: 16 B per build tuple and
+// 16 B per probe tuple (NoPartitioning: the table and a payload per build
+// tuple instead of the build columns). Groups: per element of the build
+// storage the 16-B accumulator cleared, updated and read, and 32 B per row.
+uint64_t agg_join_bytes(uint64_t nR, uint64_t nS) { return nR * 16 + nS * 16; }
+uint64_t agg_clear_bytes(uint64_t nF) { return nF * 16; }
+uint64_t agg_compact_bytes(uint64_t nF, uint64_t rows) { return nF * 16 + rows * 32; }
+
+// What the two algorithms hand to agg_passes: the build storage the
+// accumulators index and their join kernel.
+struct AggJob {
+    uint64_t nF = 0;                              // elements of the build storage
+    const NPBucket* tab = nullptr;                // NoPartitioning: the table (keys), rp = np_pays
+    const int64_t *rk = nullptr, *rp = nullptr;
+    uint64_t join_bytes = 0;
+    std::function<int(unsigned long long*, unsigned long long*)> join;   // (result words, accumulator planes)
+};
+
+// Everything behind the partitioning / table build: the result words and
+// (groups) the planes cleared, the accumulating pass, the compaction. One
+// stream, one synchronisation at the end; *end: the event behind the last kernel.
+int agg_passes(phj_ctx* c, uint32_t flags, const AggJob& J, phj_join_result* r, phj_join_totals* t, hipEvent_t* end) {
+    const bool groups = flags & PHJ_AGG_GROUPS, matched = flags & PHJ_AGG_MATCHED_ONLY;
+    const bool np = J.tab != nullptr;
+    const uint32_t fblk = static_cast<uint32_t>((J.nF + kMatBlock - 1) / kMatBlock);
+    PHJ_TRY(ensure(c, c->agg_res, 64));
+    if (groups) {
+        PHJ_TRY(ensure(c, c->agg_acc, J.nF * 16));
+        PHJ_TRY(ensure(c, c->agg_cnt, (static_cast<size_t>(fblk) + 1) * 4));
+        // (every build tuple may get a row; sized before the launch so that nothing is allocated between the passes)
+        PHJ_TRY(ensure(c, c->agg_rows, std::max<uint64_t>(1, c->side[PHJ_SIDE_BUILD].n) * sizeof(GroupRow)));
+    }
+    auto* res = static_cast<unsigned long long*>(c->agg_res.p);   // {5 totals, group rows}
+    auto* acc = static_cast<unsigned long long*>(c->agg_acc.p);
+    auto* bcnt = static_cast<uint32_t*>(c->agg_cnt.p);
+    PHJ_HIP(c, hipMemsetAsync(res, 0, 48, c->ks));
+    if (groups) {
+        const uint64_t bytes = agg_clear_bytes(J.nF);
+        r->algorithmic_bytes += bytes;
+        PHJ_TRY(timer_begin(c, "agg.groups", bytes));
+        PHJ_HIP(c, hipMemsetAsync(acc, 0, J.nF * 16, c->ks));   // on every call: never the allocation's contents
+        c->since_ev++;
+        PHJ_TRY(timer_end(c));
+    }
+    const uint64_t jbytes = J.join_bytes + (groups ? J.nF * 16 : 0);
+    r->algorithmic_bytes += jbytes;
+    PHJ_TRY(timer_begin(c, "agg.join", jbytes));
+    PHJ_TRY(J.join(res, groups ? acc : nullptr));
+    PHJ_TRY(timer_end(c));
+    const uint64_t nrows_max = c->side[PHJ_SIDE_BUILD].n;
+    if (groups) {
+        // (the rows written are only known afterwards: the timer carries the planes, the result adds the rows)
+        PHJ_TRY(timer_begin(c, "agg.groups", agg_compact_bytes(J.nF, 0)));
+        PHJ_HIP(c, hipMemsetAsync(bcnt, 0, (static_cast<size_t>(fblk) + 1) * 4, c->ks));
+        auto* rows = static_cast<GroupRow*>(c->agg_rows.p);
+        if (np) hipLaunchKernelGGL(k_agg_group_count<true>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, bcnt, res + kAggTotals);
+        else hipLaunchKernelGGL(k_agg_group_count<false>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, bcnt, res + kAggTotals);
+        PHJ_LAUNCHED(c, "k_agg_group_count");
+        PHJ_TRY(scan_u32(c, bcnt, fblk + 1, 1, fblk + 1));
+        if (np) hipLaunchKernelGGL(k_agg_group_write<true>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, J.rk, J.rp, bcnt, rows, nrows_max);
+        else hipLaunchKernelGGL(k_agg_group_write<false>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, J.rk, J.rp, bcnt, rows, nrows_max);
+        PHJ_LAUNCHED(c, "k_agg_group_write");
+        PHJ_TRY(timer_end(c));
+    }
+    PHJ_TRY(mark(c, end));
+    unsigned long long h[kAggTotals + 1] = {0, 0, 0, 0, 0, 0};
+    PHJ_HIP(c, hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, c->ks));
+    PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    PHJ_TRY(check_chunk_errors(c));
+    t->pairs = h[0];
+    t->probe_matched = h[1];
+    t->sum_a = static_cast<int64_t>(h[2]);
+    t->sum_b = static_cast<int64_t>(h[3]);
+    t->sum_ab = static_cast<int64_t>(h[4]);
+    r->matches = t->pairs;
+    if (groups) {
+        if (h[kAggTotals] > nrows_max) return set_err(c, PHJ_ERR_STATE, "phj_join_aggregate: more group rows than build tuples");
+        c->agg_n = h[kAggTotals];
+        r->algorithmic_bytes += agg_compact_bytes(J.nF, c->agg_n);
+    }
+    return PHJ_OK;
+}
+
+int join_nopart_agg(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_join_result* r, phj_join_totals* t) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
+        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
+    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (S.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    NPHome g{};
+    hipEvent_t e0 = nullptr, e1, e2;
+    PHJ_TRY(np_build(c, p, true, g, &e0));
+    PHJ_TRY(mark(c, &e1));
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
+    const auto* S_rel = reinterpret_cast<const longlong2*>(S.rel);
+    const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
+    const auto* pays = static_cast<const int64_t*>(c->np_pays.p);
+    const uint64_t table_bytes = static_cast<uint64_t>(g.nb) * 64;
+    AggJob J;
+    J.nF = static_cast<uint64_t>(g.nb) * kNPSlots;
+    J.tab = tab;
+    J.rp = pays;
+    J.join_bytes = agg_join_bytes(0, S.n) + table_bytes + R.n * 8;
+    J.join = [&](unsigned long long* res, unsigned long long* acc) -> int {
+        with_hash(p->hash, [&](auto h) {
+            constexpr int HK = decltype(h)::value;
+            if (acc)
+                hipLaunchKernelGGL((k_np_agg<HK, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
+                                   p->hash_seed, res, acc, J.nF);
+            else
+                hipLaunchKernelGGL((k_np_agg<HK, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
+                                   p->hash_seed, res, acc, J.nF);
+        });
+        PHJ_LAUNCHED(c, "k_np_agg");
+        return PHJ_OK;
+    };
+    r->algorithmic_bytes = R.n * 32 + table_bytes;
+    PHJ_TRY(agg_passes(c, flags, J, r, t, &e2));
+    r->partition_ms = 0;
+    r->build_ms = elapsed(c, e0, e1);
+    r->probe_ms = elapsed(c, e1, e2);
+    r->total_ms = elapsed(c, e0, e2);
+    r->num_partitions = 0;
+    return fill_timers(c, r);
+}
+
+// The radix form: join_radix_inner's precondition and partitioning.
+int join_radix_agg(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_join_result* r, phj_join_totals* t) {
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    const SideState& S = c->side[PHJ_SIDE_PROBE];
+    if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    FusedJoin j;
+    PHJ_TRY(fused_setup(c, p, "radix aggregate join", j));
+    AggJob J;
+    J.nF = R.view.n;
+    J.rk = R.view.keys;
+    J.rp = R.view.payloads;
+    J.join_bytes = agg_join_bytes(R.n, j.nS);
+    J.join = [&](unsigned long long* res, unsigned long long* acc) -> int {
+        hipLaunchKernelGGL(k_fused_items, dim3((j.fa.L.P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, j.fa.sbounds,
+                           j.fa.L.P, static_cast<FusedItem*>(c->fitems.p));
+        PHJ_LAUNCHED(c, "k_fused_items");
+        with_hash(j.pl.hk, [&](auto h) {
+            constexpr int HK = decltype(h)::value;
+            if (acc)
+                hipLaunchKernelGGL((k_agg_fused<HK, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, S.view.payloads,
+                                   res, acc, J.nF);
+            else
+                hipLaunchKernelGGL((k_agg_fused<HK, false>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, S.view.payloads,
+                                   res, acc, J.nF);
+        });
+        PHJ_LAUNCHED(c, "k_agg_fused");
+        return PHJ_OK;
+    };
+    r->num_partitions = j.requested;
+    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n);
+    hipEvent_t p1;
+    PHJ_TRY(agg_passes(c, flags, J, r, t, &p1));
+    return fused_times(c, j, p1, r);
+}
+
+// An empty probe side with groups of every build tuple: rows copied from the
+// bound relation, no join.
+int agg_empty_probe(phj_ctx* c, phj_join_result* r) {
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    PHJ_TRY(ensure(c, c->agg_rows, R.n * sizeof(GroupRow)));
+    hipEvent_t e0, e1;
+    PHJ_TRY(mark(c, &e0));
+    PHJ_TRY(timer_begin(c, "agg.groups", R.n * (16 + 32)));
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((R.n + kBlock - 1) / kBlock, 8192));
+    hipLaunchKernelGGL(k_agg_group_side, dim3(grid), dim3(kBlock), 0, c->ks, reinterpret_cast<const longlong2*>(R.rel),
+                       R.n, static_cast<GroupRow*>(c->agg_rows.p));
+    PHJ_LAUNCHED(c, "k_agg_group_side");
+    PHJ_TRY(timer_end(c));
+    PHJ_TRY(mark(c, &e1));
+    PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    c->agg_n = R.n;
+    r->algorithmic_bytes = R.n * (16 + 32);
+    r->probe_ms = r->total_ms = elapsed(c, e0, e1);
+    return fill_timers(c, r);
+}
+
+// phj_join_aggregate.
+int join_aggregate(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_join_result* r, phj_join_totals* t) {
+    const char* what = "phj_join_aggregate";
+    if (!c || !r || !t) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    (void)hipGetLastError();
+    if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
+    if ((flags & ~static_cast<uint32_t>(PHJ_AGG_GROUPS | PHJ_AGG_MATCHED_ONLY)) ||
+        ((flags & PHJ_AGG_MATCHED_ONLY) && !(flags & PHJ_AGG_GROUPS)))
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": flags must be 0, PHJ_AGG_GROUPS or PHJ_AGG_GROUPS | PHJ_AGG_MATCHED_ONLY");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    std::memset(r, 0, sizeof(*r));
+    std::memset(t, 0, sizeof(*t));
+    c->defer_timers = false;
+    c->lean_timers = false;
+    c->timer_skipped = false;
+    c->count_pinned = false;
+    reset_timers(c);
+    c->agg_n = 0;
+    if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
+        return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    const uint64_t nR = c->side[PHJ_SIDE_BUILD].n, nS = c->side[PHJ_SIDE_PROBE].n;
+    // an empty side joins to nothing (no table to build, no pass to run)
+    if (nR == 0 || nS == 0) {
+        if (nR > 0 && flags == PHJ_AGG_GROUPS) PHJ_TRY(agg_empty_probe(c, r));
+        return PHJ_OK;
+    }
+    if (p->algo == PHJ_ALGO_NO_PARTITIONING) return join_nopart_agg(c, p, flags, r, t);
+    return join_radix_agg(c, p, flags, r, t);
+}
+
 // ---- rows by class (phj_outer.h): pairs, probe-only, build-only ----
 
 // What the passes of phj_join_rows must move beyond the inner join's
@@ -2885,7 +3106,7 @@ void phj_ctx_destroy(phj_ctx* c) {
             free_buf(*b);
     }
     for (DevBuf* b : {&c->ht_tab, &c->ht_desc, &c->r_codes, &c->r_bounds, &c->scan_partials, &c->prep, &c->tkeys, &c->tpays, &c->toffs, &c->gcursor, &c->items, &c->biglist,
-                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->cl_done, &c->hot})
+                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->agg_acc, &c->agg_cnt, &c->agg_rows, &c->agg_res, &c->cl_done, &c->hot})
         free_buf(*b);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     for (hipEvent_t e : {c->hot_fork, c->hot_join})
@@ -3558,6 +3779,28 @@ int phj_joined_download(phj_ctx* c, phj_joined* host, uint64_t n) {
     if (!host) return set_err(c, PHJ_ERR_INVALID, "null destination");
     PHJ_HIP(c, hipSetDevice(c->device));
     PHJ_HIP(c, hipMemcpyAsync(host, c->mat_rows.p, n * sizeof(phj_joined), hipMemcpyDeviceToHost, c->stream));
+    PHJ_HIP(c, hipStreamSynchronize(c->stream));
+    return PHJ_OK;
+}
+
+int phj_join_aggregate(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_join_result* r, phj_join_totals* t) {
+    return join_aggregate(c, p, flags, r, t);
+}
+
+const phj_group_row* phj_group_rows(phj_ctx* c, uint64_t* n) {
+    if (!c || c->group) return nullptr;
+    if (n) *n = c->agg_n;
+    return static_cast<const phj_group_row*>(c->agg_rows.p);
+}
+
+int phj_group_download(phj_ctx* c, phj_group_row* host, uint64_t n) {
+    if (!c) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_group_download: single-device contexts only");
+    if (n > c->agg_n) return set_err(c, PHJ_ERR_RANGE, "more rows requested than the last aggregate join made");
+    if (n == 0) return PHJ_OK;
+    if (!host) return set_err(c, PHJ_ERR_INVALID, "null destination");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_HIP(c, hipMemcpyAsync(host, c->agg_rows.p, n * sizeof(phj_group_row), hipMemcpyDeviceToHost, c->stream));
     PHJ_HIP(c, hipStreamSynchronize(c->stream));
     return PHJ_OK;
 }

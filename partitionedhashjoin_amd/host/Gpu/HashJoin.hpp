@@ -20,6 +20,10 @@
 // results as `pairs`, `probe_only`, `build_only`); the matched
 // count (MaterializeAll: the pair count, RowClasses: the row count) is logged ("Joined N tuples", RadixCluster/HashJoin.hpp:320-321),
 // added to the results as `matches`, and kept in GetNumberOfJoinedTuples().
+// GpuConfiguration::Aggregate asks for the join's aggregates instead of rows
+// (phj_join_aggregate: `pairs`, `probe_matched`, `sum_a`, `sum_b`, `sum_ab`
+// added to the results; for groups also `groups` and `groups_checksum` over
+// the group rows copied back); the returned table is empty, matches = pairs.
 // C ABI errors surface as std::runtime_error / std::invalid_argument, which the
 // CLI catches and turns into exit(1) (src/main.cpp:277-281).
 #pragma once
@@ -93,6 +97,28 @@ inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, con
                                                                 const Common::GpuConfiguration& gpu,
                                                                 Common::IHashJoinTimer& timer) {
     const bool materialize = gpu.Materialize, all = gpu.MaterializeAll;
+    if (gpu.Aggregate != 0) {
+        phj_join_totals t{};
+        dev.Check(phj_join_aggregate(dev.Get(), &p, gpu.Aggregate == 2 ? PHJ_AGG_GROUPS : 0u, &r, &t));
+        timer.AddResult("pairs", std::to_string(t.pairs));
+        timer.AddResult("probe_matched", std::to_string(t.probe_matched));
+        timer.AddResult("sum_a", std::to_string(t.sum_a));
+        timer.AddResult("sum_b", std::to_string(t.sum_b));
+        timer.AddResult("sum_ab", std::to_string(t.sum_ab));
+        if (gpu.Aggregate == 2) {
+            uint64_t n = 0;
+            (void)phj_group_rows(dev.Get(), &n);
+            std::vector<phj_group_row> rows(n);
+            dev.Check(phj_group_download(dev.Get(), rows.data(), n));
+            uint64_t sum = 0;   // (order-free, as the rows' order is unspecified)
+            for (const phj_group_row& g : rows)
+                sum += static_cast<uint64_t>(g.id) * 3 + static_cast<uint64_t>(g.payload_a) * 5 + g.partners * 7 +
+                       static_cast<uint64_t>(g.sum_b) * 11;
+            timer.AddResult("groups", std::to_string(n));
+            timer.AddResult("groups_checksum", std::to_string(sum));
+        }
+        return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());
+    }
     if (gpu.RowClasses != 0) {
         phj_row_counts n{};
         dev.Check(phj_join_rows(dev.Get(), &p, gpu.RowClasses, gpu.NullPayload, &r, &n));

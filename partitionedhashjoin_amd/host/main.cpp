@@ -17,6 +17,7 @@
 //   --gpus N | --devices a,b,..  several devices (multi-GPU join over RCCL)
 //   --exchange rccl|local  force the multi-GPU path (RCCL world of one / device copies)
 //   --join-kind K         inner|probe-outer|build-outer|full-outer|probe-anti|build-anti: return that kind's rows
+//   --aggregate A         totals|groups: report the join's aggregates instead of rows
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -69,6 +70,10 @@ const char* kHelp =
     "  --join-kind arg                     inner | probe-outer | build-outer | full-outer | probe-anti | build-anti:\n"
     "                                      return that join's rows; a tuple without a partner gets INT64_MIN\n"
     "                                      as the missing side's payload.\n"
+    "  --aggregate arg                     totals | groups: aggregate over the inner join without its rows:\n"
+    "                                      pairs, probe_matched, sum_a, sum_b, sum_ab; groups: also one row per\n"
+    "                                      build tuple {partners, sum of their payloads}, reported as a count\n"
+    "                                      and a checksum. One device only, and not together with returned rows.\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
@@ -103,7 +108,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
     static const std::set<std::string> known = {"help", "primary", "secondary", "skew", "log", "join", "format",
                                                 "unit", "output", "filename", "partitions", "device", "gpus", "devices", "exchange", "hash",
                                                 "radix-bits", "seed", "hash-seed", "generate", "table-ratio",
-                                                "materialize", "join-kind"};
+                                                "materialize", "join-kind", "aggregate"};
     Common::Configuration c{};
     c.OutputFormatConfig.TimeUnit = "ms";
     c.OutputConfig.File.Name = "hashjoin.txt";
@@ -169,6 +174,11 @@ Common::Configuration parseArguments(int argc, char** argv) {
                 throw std::invalid_argument("the argument ('" + vm["join-kind"] + "') for option '--join-kind' is invalid");
             c.GpuConfig.RowClasses = k->second;
         }
+        if (vm.count("aggregate")) {
+            if (vm["aggregate"] == "totals") c.GpuConfig.Aggregate = 1;
+            else if (vm["aggregate"] == "groups") c.GpuConfig.Aggregate = 2;
+            else throw std::invalid_argument("the argument ('" + vm["aggregate"] + "') for option '--aggregate' is invalid");
+        }
         c.GpuConfig.Hash = PHJ_HASH_XXH3;
         if (vm.count("hash")) {
             if (vm["hash"] == "xxh3" || vm["hash"] == "xxhash") c.GpuConfig.Hash = PHJ_HASH_XXH3;
@@ -227,6 +237,10 @@ Common::Configuration parseArguments(int argc, char** argv) {
             throw std::invalid_argument("--join-kind returns its own rows: not together with --materialize on / all");
         if (c.GpuConfig.RowClasses && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--join-kind runs on one device");
+        if (c.GpuConfig.Aggregate && (c.GpuConfig.Materialize || c.GpuConfig.MaterializeAll || c.GpuConfig.RowClasses))
+            throw std::invalid_argument("--aggregate returns no rows: not together with --materialize on / all or --join-kind");
+        if (c.GpuConfig.Aggregate && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
+            throw std::invalid_argument("--aggregate runs on one device");
         // validateParsedConfiguration (src/Arguments.hpp:7-18)
         c.OutputConfig.Validate();
         c.OutputFormatConfig.Validate();
