@@ -232,7 +232,12 @@ struct phj_ctx {
     // hot-key pre-aggregation (phj_hot.h): the state; phj_debug_preagg's mode
     // (0 auto, 1 off, 2 forced); hot_on: the running join's probe-side code
     // pass takes its HOT form; hot_ran / hot_n / hot_min_mass: the last join's, for its statistics
+    // hot_clean / hot_clean_nb: the buffer and cluster count for which the
+    // counters and control words are known to be zero (k_hot_select's
+    // clearing); else the next prologue starts with k_hot_clear
     DevBuf hot;
+    void* hot_clean = nullptr;
+    uint32_t hot_clean_nb = 0;
     int hot_mode = 0;
     bool hot_on = false, hot_ran = false;
     uint64_t hot_n = 0;
@@ -1157,8 +1162,8 @@ int partition_side(phj_ctx* c, int s, const Plan& pl, bool p1_only = false, unsi
 // default schedule (PHJ_R_ORDER=1, R in tile mode): whether this join takes
 // it. A host-side decision: both code passes must be the 1024 x 4 pipelined
 // form with one digit per thread (the LDS holds the table beside S's pass's
-// own 90 KB up to 1024 clusters), R's tile list must be the one k_hot_resolve
-// scans, and S must be large enough that the sample
+// own 90 KB up to 1024 clusters), R's tile list must be the one the LDS join
+// reads (it resolves the hot weights), and S must be large enough that the sample
 // (kHotTiles tiles, two reads) is small against its pass: 32 times the sample.
 constexpr uint64_t kHotMinS = 32ull * kHotTiles * kHotTile;   // 16.8M tuples
 bool hot_wanted(const phj_ctx* c, const Plan& cpl, uint64_t nS, uint64_t nR) {
@@ -1191,55 +1196,38 @@ int hot_begin(phj_ctx* c, const Plan& cpl, const SideState& S) {
     h.w = h.code + static_cast<size_t>(cpl.nb1) * kHotPer;
     h.ctl = reinterpret_cast<uint32_t*>(h.w + static_cast<size_t>(cpl.nb1) * kHotPer);
     h.rep = reinterpret_cast<unsigned long long*>(h.ctl + kHotCtlWords);
-    // a table covering under an eighth of the sample is ignored by S's pass and k_hot_resolve
+    // a table covering under an eighth of the sample is ignored by S's pass and the LDS join
     c->hot_min_mass = forced ? 0u : static_cast<uint32_t>(std::min<uint64_t>(S.n, static_cast<uint64_t>(h.nsamp) * kHotTile) / 8);
     c->hot_n = S.n;
     // no timer events under PHJ_LEAN_TIMERS (each one between two kernels costs ~4 us)
     const bool timed = !c->lean_timers;
-    if (timed) PHJ_TRY(timer_begin(c, "S.hot", 2ull * h.nsamp * kHotTile * 16));
+    if (timed) PHJ_TRY(timer_begin(c, "S.hot", 1ull * h.nsamp * kHotTile * 16));
     const void* ksample = with_hash(cpl.hk, [](auto hh) { return reinterpret_cast<const void*>(&k_hot_sample<decltype(hh)::value>); });
-    // auto mode: a first look at an eighth of the sample's tiles; without skew there the rest returns at once
+    // auto mode: a sample workgroup whose own tiles show no skew writes nothing
     h.staged = !forced && h.nsamp == kHotTiles ? 1u : 0u;
-    hipLaunchKernelGGL(k_hot_clear, dim3(16), dim3(kHotBlock), 0, c->ks, h);
-    PHJ_LAUNCHED(c, "k_hot_clear");
-    uint32_t phase = h.staged ? 1u : 0u;
-    void* sargs[] = {&h, &phase};
-    const uint32_t first = (h.nsamp + kHotStage - 1) / kHotStage;
+    // the counters and control words: left zero by the last join's selection,
+    // unless this is another buffer or layout, or that selection did not run
+    // (hot_clean is set again once this join's has been launched, and dropped
+    // by a join that fails)
+    const bool clean = c->hot_clean == c->hot.p && c->hot_clean_nb == cpl.nb1;
+    c->hot_clean = nullptr;
+    if (!clean) {
+        hipLaunchKernelGGL(k_hot_clear, dim3(16), dim3(kHotBlock), 0, c->ks, h);
+        PHJ_LAUNCHED(c, "k_hot_clear");
+    }
+    void* sargs[] = {&h};
     // (kHotTilesPerWg sample tiles per workgroup, one workgroup of selection:
     // at most 32 workgroups at a time, so R's pass 1 can run beside them)
     const uint32_t wide = (h.nsamp + kHotTilesPerWg - 1) / kHotTilesPerWg;
-    PHJ_TRY(launch_kernel(c, ksample, dim3(h.staged ? first : wide), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
-    if (h.staged) {
-        phase = 2;
-        PHJ_TRY(launch_kernel(c, ksample, dim3(wide), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
-    }
+    PHJ_TRY(launch_kernel(c, ksample, dim3(wide), dim3(kHotBlock), sargs, kHotCounters * 2, "k_hot_sample"));
     hipLaunchKernelGGL(k_hot_select, dim3(1), dim3(kHotBlock), hot_select_lds_bytes(cpl.nb1), c->ks, h);
     PHJ_LAUNCHED(c, "k_hot_select");
+    c->hot_clean = c->hot.p;
+    c->hot_clean_nb = cpl.nb1;
     if (timed) PHJ_TRY(timer_end(c));
     c->hot_on = true;
     c->hot_ran = true;
     return PHJ_OK;
-}
-
-// The hot weights of the entries R holds, added to the count (k_hot_resolve):
-// on the main stream after S's pass-1 bookkeeping (which clears the count) and
-// after R's chain (RT: R's chunked code pass, its tile list).
-int hot_resolve(phj_ctx* c, const Plan& cpl, const SideState& RT) {
-    HotResolveArgs a{};
-    const uint32_t* st = static_cast<const uint32_t*>(c->hot.p);
-    a.code = reinterpret_cast<const unsigned long long*>(st + kHotCounters);
-    a.w = a.code + static_cast<size_t>(cpl.nb1) * kHotPer;
-    a.ctl = reinterpret_cast<const uint32_t*>(a.w + static_cast<size_t>(cpl.nb1) * kHotPer);
-    a.min_mass = c->hot_min_mass;
-    a.rt_base = RT.p2.tile_base;
-    a.rt_start = RT.p2.tile_start;
-    a.rt_cnt = RT.p2.tile_cnt;
-    a.r_pool = RT.p2.in_keys;
-    a.count = static_cast<unsigned long long*>(c->count.p);
-    PHJ_TRY(timer_begin(c, "R.hot", RT.n * 8));   // (an R timer: none under PHJ_LEAN_TIMERS)
-    hipLaunchKernelGGL(k_hot_resolve, dim3(cpl.nb1), dim3(kHotResolveBlock), 0, c->ks, a);
-    PHJ_LAUNCHED(c, "k_hot_resolve");
-    return timer_end(c);
 }
 
 // Build over `nseg` partitioned build segments and probe the ctx's partitioned
@@ -1789,8 +1777,18 @@ int probe_cluster(phj_ctx* c, const Plan& pl, SideState& PS, int nseg, const int
     // three tiles of codes in flight, the next cluster's R codes prefetched
     // (measured: one / two tiles 0.406 / 0.360 ms against 0.355 at C2; tables by
     // 64-bit compare-and-swap 0.082 ms of builds against 0.055 by fill counters)
-    const void* kfn = RT ? reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, true>)
-                         : reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, false>);
+    // with the hot table of S's pass 1 (hot_begin), the join resolves its
+    // weights: the entries R holds add theirs to the count (an empty R holds none)
+    if (c->hot_on && RT && &PS == &c->side[PHJ_SIDE_PROBE]) {
+        const uint32_t* st = static_cast<const uint32_t*>(c->hot.p);
+        a.hot_code = reinterpret_cast<const unsigned long long*>(st + kHotCounters);
+        a.hot_w = a.hot_code + static_cast<size_t>(pl.nb1) * kHotPer;
+        a.hot_ctl = reinterpret_cast<const uint32_t*>(a.hot_w + static_cast<size_t>(pl.nb1) * kHotPer);
+        a.hot_min_mass = c->hot_min_mass;
+    }
+    const void* kfn = !RT          ? reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, false>)
+                      : a.hot_code ? reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, true, true>)
+                                   : reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, true>);
     int per_cu = 0;
     if ((per_cu = occupancy(kfn, B, lds)) < 1) per_cu = 1;
     per_cu = std::max(1, std::min<int>(per_cu, static_cast<int>(160 * 1024 / (lds + 256))));
@@ -3414,8 +3412,8 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         // chain on the aux stream from the join's start, beside the hot-key
         // prologue (a few narrow kernels bound by atomics), its pass 1 leaving
         // the prologue PHJ_HOT_FREE_CUS CUs per shard; the main stream waits
-        // for it before k_hot_resolve. R's chain reads nothing of S's: the
-        // weights are resolved by k_hot_resolve, not by R's pass
+        // for it before the LDS join. R's chain reads nothing of S's: the
+        // weights are resolved by the LDS join, not by R's pass
         const bool hot = hot_wanted(c, cpl, S.n, R.n);
         const bool early_r = PHJ_HOT_EARLY_R != 0 && hot && R.n > 0;
         auto r_chain = [&](hipEvent_t after) -> int {
@@ -3466,19 +3464,23 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
             c->p1_clear_bytes = chunk_state_bytes(cpl.nb1);
         }
         if (early_r) {
-            // the fork, before the prologue: the previous join's probe and
-            // k_hot_resolve read R's pool and tile list
+            // the fork, before the prologue: the previous join's probe
+            // read R's pool and tile list
             for (hipEvent_t* e : {&c->hot_fork, &c->hot_join})
                 if (!*e && !(*e = new_event())) return set_err(c, PHJ_ERR_HIP, "hipEventCreate failed");
             PHJ_HIP(c, hipEventRecord(c->hot_fork, c->stream));
         }
         // hot probe keys (phj_hot.h): sampled and selected here; S's pass then
-        // counts them instead of writing them, k_hot_resolve adds the weights
-        // of those R holds to the count (after S's bookkeeping kernel has
-        // cleared it: one stream)
+        // counts them instead of writing them, the LDS join looks them up in
+        // the tables it builds and adds the weights of those R holds to the
+        // count (after S's bookkeeping kernel has cleared it: one stream)
         struct HotScope {
             phj_ctx* c;
-            ~HotScope() { c->hot_on = false; }
+            bool ok = false;   // the join ran to its end (else the hot state is cleared before its next use)
+            ~HotScope() {
+                c->hot_on = false;
+                if (!ok) c->hot_clean = nullptr;
+            }
         } hot_scope{c};
         if (hot) PHJ_TRY(hot_begin(c, cpl, S));
         if (early_r) {
@@ -3504,10 +3506,7 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         }
         if (!r_main) PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
         if (early_r) PHJ_HIP(c, hipStreamWaitEvent(c->stream, c->hot_join, 0));
-        if (c->hot_on && R.n > 0) {
-            if (!RT) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs R's chunked code pass");
-            PHJ_TRY(hot_resolve(c, cpl, *RT));
-        }
+        if (c->hot_on && R.n > 0 && !RT) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs R's chunked code pass");
         PHJ_TRY(phase_mark(&t1));
         // one launch, reported as "build" (the workgroups' table builds in LDS:
         // R's codes read) and "probe" (S's codes read), split by the kernel's own clocks
@@ -3533,6 +3532,7 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         r->num_partitions = requested;
         // R: 16 read + 8 written (pass 1), 8 read (probe); S: 16 read + 8 written, 8 read
         r->algorithmic_bytes = R.n * (24 + 8) + S.n * (24 + 8);
+        hot_scope.ok = true;
         return fill_timers(c, r);
     }
     refine_plan(c, pl, R.n);

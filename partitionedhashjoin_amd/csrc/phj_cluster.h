@@ -99,7 +99,21 @@ struct ClusterArgs {
     // join's pass 1 then skips its memset)
     uint4* s_clear;
     uint32_t s_clear16;
+    // the hot table of S's pass 1 (phj_hot.h; tile mode only), or null: its
+    // entries that R holds add their weights to the count (a hot entry is a
+    // probe code that carries a weight). [nb1][kHotPer] codes and weights (the
+    // weights right behind the codes), the control words, and the coverage
+    // under which S's pass ignored the table
+    const unsigned long long* hot_code;
+    const unsigned long long* hot_w;
+    const uint32_t* hot_ctl;
+    uint32_t hot_min_mass;
 };
+
+// Whether S's pass 1 used the hot table (its own test; grid-uniform).
+__device__ __forceinline__ bool cl_hot_live(const ClusterArgs& a) {
+    return a.hot_code && a.hot_ctl[kHotCtlEntries] != 0 && a.hot_ctl[kHotCtlMass] >= a.hot_min_mass;
+}
 
 // A cluster's table is in HBM (k_cluster_big_fill / k_cluster_probe_big):
 // more codes than the LDS table holds, or (tile mode) more runs than a build
@@ -115,11 +129,22 @@ constexpr int kClProfWords = 6;
 // over all segments). Wave 0 computes, every thread sees it after the caller's barrier.
 // TM: 1 = tile mode, 0 = segment mode, -1 = decided by a.rt_base (the big
 // kernels); the probe is instantiated per mode (one path's registers each).
-template <int TM = -1>
+// HOT (tile mode): the cluster's hot entries are staged with its runs, shot =
+// kHotPer codes, then their kHotPer weights, by lanes of wave 1 in a block of
+// their own, the table's address read from LDS (*hotp = a.hot_code; the
+// weights follow the codes). Staged inside wave 0's block through the two
+// kernel arguments, the probe spilled to scratch (its reloads queue with the
+// tile loads: probe 0.161 -> 0.206 ms at C2); this way it keeps 128 VGPRs and none.
+template <int TM = -1, bool HOT = false>
 __device__ __forceinline__ void cl_runs(const ClusterArgs& a, uint32_t d, uint32_t* sseg, const int64_t** sptr,
-                                        uint32_t* sB, uint32_t* sM, uint32_t* sN) {
+                                        uint32_t* sB, uint32_t* sM, uint32_t* sN, unsigned long long* shot = nullptr,
+                                        const unsigned long long* const* hotp = nullptr) {
     const uint32_t tid = threadIdx.x;
     if (TM == 1 || (TM == -1 && a.rt_base)) {   // tile mode: the cluster's R tiles are its runs
+        if (HOT && tid - 64u < 2 * kHotPer) {
+            const uint32_t j = tid - 64u;
+            shot[j] = (*hotp)[d * kHotPer + (j < kHotPer ? j : a.nb1 * kHotPer + j - kHotPer)];
+        }
         if (tid < 64) {
             const uint32_t t0 = a.rt_base[d], nt = a.rt_base[d + 1] - t0;
             uint32_t lo = 0, len = 0;
@@ -238,14 +263,28 @@ __global__ __launch_bounds__(256) void k_cluster_probe_big(ClusterArgs a) {
     __shared__ uint32_t sB, sM, sN;
     __shared__ uint32_t red[4];
     __shared__ uint32_t list[256], nlist;
+    __shared__ uint32_t hlist[256], nhlist, met[kHotPer];
     const uint32_t tid = threadIdx.x, G = gridDim.x;
-    if (tid == 0) nlist = 0;
+    if (tid == 0) nlist = nhlist = 0;
     __syncthreads();
-    for (uint32_t d = blockIdx.x + tid * G; d < a.nb1; d += 256 * G)
-        if (cl_is_big(a, d)) list[atomicAdd(&nlist, 1u)] = d;   // (<= 256: nb1 <= 256 * grid)
+    // the hot weights (phj_hot.h) of the clusters k_cluster_probe never
+    // builds: the big ones, and those S's pass left without a tile (every S
+    // tuple of theirs was counted into a weight)
+    const bool hot = a.rt_base && cl_hot_live(a);   // grid-uniform
+    for (uint32_t d = blockIdx.x + tid * G; d < a.nb1; d += 256 * G) {
+        if (cl_is_big(a, d)) {
+            list[atomicAdd(&nlist, 1u)] = d;   // (<= 256: nb1 <= 256 * grid)
+        } else if (hot && a.tile_base[d] == a.tile_base[d + 1]) {
+            bool any = false;
+#pragma unroll
+            for (uint32_t k = 0; k < kHotPer; k++) any = any || a.hot_w[static_cast<size_t>(d) * kHotPer + k] != 0;
+            if (any) hlist[atomicAdd(&nhlist, 1u)] = d;
+        }
+    }
     __syncthreads();
-    const uint32_t nbig = nlist;
+    const uint32_t nbig = nlist, nhot = nhlist;
     uint32_t hits = 0;
+    unsigned long long hsum = 0;   // weights of the hot entries R holds
     for (uint32_t k = 0; k < nbig; k++) {
         const uint32_t d = list[k];
         cl_runs(a, d, sseg, sptr, &sB, &sM, &sN);
@@ -270,9 +309,67 @@ __global__ __launch_bounds__(256) void k_cluster_probe_big(ClusterArgs a) {
                 }
             }
         }
+        if (hot && tid < kHotPer) {   // the cluster's hot entries: probe codes that carry a weight
+            const uint64_t cc = a.hot_code[static_cast<size_t>(d) * kHotPer + tid];
+            const unsigned long long wt = a.hot_w[static_cast<size_t>(d) * kHotPer + tid];
+            if (wt != 0) {
+                uint32_t b = static_cast<uint32_t>(cc >> kHtBucketShift) & bmask;
+                for (;;) {
+                    const ulonglong2 w = g2[b];
+                    if (w.x == cc || w.y == cc) {
+                        hsum += wt;
+                        break;
+                    }
+                    if (w.y == e) break;
+                    b = (b + 1) & bmask;
+                }
+            }
+        }
     }
-    if (nbig == 0 && !a.host_out) return;   // workgroup-uniform
+    // a tile-less cluster below the LDS limit: its R codes scanned tile by tile
+    // through R's pass-1 tile list for its entries (a wave per tile; a key R
+    // holds twice counts once, as in the probe's set test)
+    for (uint32_t k = 0; k < nhot; k++) {
+        const uint32_t d = hlist[k];
+        unsigned long long hc[kHotPer], hw[kHotPer];
+#pragma unroll
+        for (uint32_t q = 0; q < kHotPer; q++) {
+            hc[q] = a.hot_code[static_cast<size_t>(d) * kHotPer + q];
+            hw[q] = a.hot_w[static_cast<size_t>(d) * kHotPer + q];
+        }
+        if (tid < kHotPer) met[tid] = 0;
+        __syncthreads();
+        constexpr uint32_t U = 8;
+        const uint32_t l = tid & 63;
+        for (uint32_t ti = a.rt_base[d] + (tid >> 6); ti < a.rt_base[d + 1]; ti += 4) {
+            const int64_t* src = a.r_pool + a.rt_start[ti];
+            const uint32_t c = a.rt_cnt[ti];
+            for (uint32_t r0 = 0; r0 < c; r0 += U * 64) {
+                unsigned long long v[U];
+#pragma unroll
+                for (uint32_t u = 0; u < U; u++) {
+                    const uint32_t r = r0 + u * 64 + l;
+                    v[u] = static_cast<unsigned long long>(src[r < c ? r : 0]);
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < U; u++) {
+                    if (r0 + u * 64 + l >= c) continue;
+#pragma unroll
+                    for (uint32_t q = 0; q < kHotPer; q++)
+                        if (v[u] == hc[q] && hw[q] != 0) met[q] = 1;
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < kHotPer && met[tid]) hsum += a.hot_w[static_cast<size_t>(d) * kHotPer + tid];
+        __syncthreads();   // (met read before the next cluster clears it)
+    }
+    if (nbig == 0 && nhot == 0 && !a.host_out) return;   // workgroup-uniform
     __shared__ uint32_t clear_state;
+    if (hsum) {   // (in before thread 0 reports this workgroup done)
+        atomicAdd(a.count, hsum);
+        __threadfence();
+    }
     uint32_t x = hits;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
@@ -321,14 +418,30 @@ __host__ __device__ constexpr size_t cluster_lds_bytes(uint32_t cap) { return st
 #ifndef PHJ_CL_ASM
 #define PHJ_CL_ASM 1
 #endif
-template <int BLOCK, int ITEMS, int PF = 1, bool PRE = true, bool PROF = false, bool TM = false, bool ASMW = PHJ_CL_ASM != 0>
+// HOTR (tile mode, with the hot table of S's pass 1: phj_hot.h): a cluster's
+// hot entries are looked up in its table once it is built, as an S code is, and
+// the weights of those found join the hits. The workgroup whose range holds the
+// cluster's first S tile does it (a cluster at a range boundary is built by
+// two or more workgroups): every cluster but the one of tile t_lo - 1. The
+// entries come with the cluster's runs (cl_runs), so the loop's loads stay
+// the same on every path. Clusters never built here (big, or without an S
+// tile) are k_cluster_probe_big's.
+template <int BLOCK, int ITEMS, int PF = 1, bool PRE = true, bool PROF = false, bool TM = false, bool HOTR = false,
+          bool ASMW = PHJ_CL_ASM != 0>
 __global__ __launch_bounds__(BLOCK) void k_cluster_probe(ClusterArgs a) {
+    static_assert(!HOTR || TM, "the hot entries are staged with a cluster's R tiles");
     constexpr int CPL = kClCapMax * 3 / 4 / BLOCK;   // R codes per lane at the limit
     extern __shared__ __attribute__((aligned(16))) uint64_t tab[];   // [cap] + cap / 4 words of fill counters
     uint32_t* const fill = reinterpret_cast<uint32_t*>(tab + a.cap);
     __shared__ uint32_t sseg_[2][kHtSegs + 1];
     __shared__ const int64_t* sptr_[2][kHtSegs];
     __shared__ uint32_t sB_[2], sM_[2], sN_[2];   // first code, codes, runs of the cluster in each run buffer
+    // HOTR: the cluster's hot codes, then their weights; the weights of the
+    // entries found; {S's pass used the table, the one cluster of this range that
+    // another workgroup owns}. All in LDS: no register lives through the tile loop
+    __shared__ unsigned long long shot_[2][HOTR ? 2 * kHotPer : 1], shsum;
+    __shared__ const unsigned long long* shotp;   // a.hot_code (cl_runs)
+    __shared__ uint32_t shctl[2];
     __shared__ uint32_t red[BLOCK / 64];
     constexpr uint32_t MR = 512;                 // tiles of metadata staged in LDS at a time
     __shared__ uint32_t smeta[3][MR];            // {cluster, first slot, codes} of tiles mbase .. mbase + MR - 1
@@ -406,6 +519,16 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_probe(ClusterArgs a) {
                 m |= (e < c ? (1u << i) : 0u) | (e + 1 < c ? (2u << i) : 0u);
             }
         };
+        // HOTR: read here, once, ahead of the first staging (which waits for
+        // every load and has the barriers): no load of it in the loop
+        if constexpr (HOTR) {
+            if (tid == 0) {
+                shsum = 0;
+                shotp = a.hot_code;
+                shctl[0] = cl_hot_live(a) ? 1u : 0u;
+                shctl[1] = t_lo ? a.tile_seg[t_lo - 1] : 0xffffffffu;
+            }
+        }
         stage(t_lo);
 #pragma unroll
         for (int f = 0; f < PF; f++) load(t_lo + f, kv[f], vm[f], dq[f]);   // tiles t_lo .. t_lo + PF - 1
@@ -458,7 +581,7 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_probe(ClusterArgs a) {
 #pragma unroll
                 for (int j = 0; j < CPL; j++) rc[j] = rn[PRE ? j : 0];
             } else {
-                cl_runs<TM ? 1 : 0>(a, d, sseg_[pb], sptr_[pb], &sB_[pb], &sM_[pb], &sN_[pb]);
+                cl_runs<TM ? 1 : 0, HOTR>(a, d, sseg_[pb], sptr_[pb], &sB_[pb], &sM_[pb], &sN_[pb], shot_[pb], &shotp);
                 __syncthreads();
                 const uint32_t m0 = sM_[pb];
                 if (!cl_big(m0, sN_[pb], a.lim)) fetch(pb, m0, rc);
@@ -479,7 +602,9 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_probe(ClusterArgs a) {
             }
             // the next cluster's runs into the other buffer (read after the barrier)
             const bool nxt = PRE && d < d_last;
-            if (nxt) cl_runs<TM ? 1 : 0>(a, d + 1, sseg_[pb ^ 1u], sptr_[pb ^ 1u], &sB_[pb ^ 1u], &sM_[pb ^ 1u], &sN_[pb ^ 1u]);
+            if (nxt)
+                cl_runs<TM ? 1 : 0, HOTR>(a, d + 1, sseg_[pb ^ 1u], sptr_[pb ^ 1u], &sB_[pb ^ 1u], &sM_[pb ^ 1u], &sN_[pb ^ 1u],
+                                          shot_[pb ^ 1u], &shotp);
             __syncthreads();   // cleared; the next runs staged
             if (PROF) c2 = wall_clock64();
             if (!big) {
@@ -524,6 +649,27 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_probe(ClusterArgs a) {
                 }
             }
             __syncthreads();   // built
+            if constexpr (HOTR) {
+                // this workgroup's cluster: its hot entries walk the table as S
+                // codes do (LDS only; an empty way has no weight)
+                if (tid < kHotPer && !big && shctl[0] != 0 && d != shctl[1]) {
+                    const uint64_t cc = shot_[pb][tid];
+                    const unsigned long long wt = shot_[pb][kHotPer + tid];
+                    if (wt != 0) {
+                        const ulonglong2* t2 = reinterpret_cast<const ulonglong2*>(tab);
+                        uint32_t b = static_cast<uint32_t>(cc >> kHtBucketShift) & bmask;
+                        for (;;) {
+                            const ulonglong2 w = t2[b];
+                            if (w.x == cc || w.y == cc) {
+                                atomicAdd(&shsum, wt);
+                                break;
+                            }
+                            if (w.y == e) break;
+                            b = (b + 1) & bmask;
+                        }
+                    }
+                }
+            }
             cur = d;
             const unsigned long long c4 = wall_clock64();
             clk_b += c4 - cb;
@@ -604,6 +750,8 @@ __global__ __launch_bounds__(BLOCK) void k_cluster_probe(ClusterArgs a) {
     if (tid == 0) {
         unsigned long long s = 0;
         for (int w = 0; w < BLOCK / 64; w++) s += red[w];
+        if constexpr (HOTR)
+            if (t_lo < t_hi) s += shsum;
         if (s) atomicAdd(a.count, s);
         if (a.split) {
             const unsigned long long all = wall_clock64() - clk0;

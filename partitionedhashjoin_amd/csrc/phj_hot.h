@@ -6,11 +6,16 @@
 // "is it in R". So before S's pass 1 a strided sample of S is hashed and
 // counted, and the codes sampled often enough enter a hot table; S's pass then
 // counts a hot code into its entry's weight instead of writing it
-// (k_chunk_codes_pipe HOT 1, phj_partition.h), and after S's pass
-// k_hot_resolve scans R's codes cluster by cluster and adds the weight of
-// every entry it meets to the join's count. R's pass 1 itself has no part in
-// it, so R's chain needs nothing of S's. A code that found no way takes the
-// normal path, so any selection is exact.
+// (k_chunk_codes_pipe HOT 1, phj_partition.h). A hot entry is then a probe
+// code that carries a weight, and the LDS join resolves it where it answers
+// the same question for every other S code (phj_cluster.h): the workgroup of
+// k_cluster_probe that owns a cluster (its range holds the cluster's first S
+// tile) looks the cluster's entries up in the table it has just built and
+// adds the weights of those found to its hits; k_cluster_probe_big does it
+// for the clusters that kernel never builds (an HBM table, or no S tile left:
+// then R's codes are scanned). R's codes are read no second time. R's pass 1
+// has no part in it, so R's chain needs nothing of S's. A code that found no
+// way takes the normal path, so any selection is exact.
 //
 // The table: per cluster digit of pass 1, kHotSub sets (the code's top bit)
 // of kHotWays 64-bit codes, so a lookup needs only what the pass has computed
@@ -24,17 +29,24 @@
 // reads the counters, takes the representative of every counter at or above
 // the threshold and builds the table in LDS. The representative may be a cold
 // code that shares a hot code's counter: the hot code is then not entered.
-// Inputs without skew pay for none of this beyond a first look: in auto mode
-// a first stage counts an eighth of the sample's tiles in LDS only (no global
-// atomics: ~10 ns each per workgroup, the sample's whole cost) and adds up,
-// per tile, the keys of counters that stand out inside that one tile; unless
-// they cover a sixteenth of the stage's keys, the sample proper returns at once
-// and the selection writes an empty table (the pass skips its lookups).
+// Inputs without skew pay for none of this beyond the LDS count: in auto mode
+// a workgroup of the sample looks at its own LDS counters before anything
+// global (the global atomics, ~10 ns each per workgroup, are the sample's
+// whole cost) and adds up the keys of counters that stand out among the keys
+// it counted; unless they cover a sixteenth of them, it leaves no global trace
+// at all. A workgroup that goes on stores its representatives, flushes its
+// counters and adds its vote to a control word; without a vote the selection
+// writes an empty table at once (the pass skips its lookups), else it works
+// on what was flushed (the coverage test of S's pass is the final guard).
 // An empty way holds a code of another cluster (0, or E of cluster 0: no key
-// value is reserved). The counters and control words are cleared by
-// k_hot_clear and the table is written by k_hot_select in every join; the
-// representatives are not cleared (a counter that counts in this join was
-// written in this join): nothing is kept from the join before.
+// value is reserved). The prologue is two launches, sample and selection:
+// the selection zeroes the counters it read and the control words for the
+// next join, and the host launches k_hot_clear only when the state is not
+// known to be clean (the first join, a failed join, a new buffer or another
+// cluster count, a join whose selection did not run). The table is written by
+// k_hot_select in every join; the representatives are not cleared (a counter
+// that counts in this join was written in this join): nothing else is kept
+// from the join before, and nothing relies on what an allocation holds.
 #pragma once
 
 #include "phj_partition.h"
@@ -43,16 +55,14 @@ namespace phj {
 
 constexpr uint32_t kHotTile = 4096;        // keys of one sample tile
 constexpr uint32_t kHotTiles = 128;        // sample tiles, spread evenly over S
-constexpr uint32_t kHotTilesPerWg = 4;     // sample tiles of one workgroup of k_hot_sample (phases 0 and 2)
+constexpr uint32_t kHotTilesPerWg = 4;     // sample tiles of one workgroup of k_hot_sample
 constexpr uint32_t kHotCounters = 65536;   // sample counters (L2-resident, 256 KB), 16 bits each in the workgroups' LDS
 constexpr uint32_t kHotThreshold = 16;     // sample count of a hot code at kHotTiles tiles (3.1e-5 of S)
 constexpr uint32_t kHotHeavy = 8;          // codes sampled this many thresholds over are entered first
 constexpr uint32_t kHotBlock = 1024;
-constexpr uint32_t kHotStage = 8;          // auto mode: every 8th sample tile is the first stage
-constexpr uint32_t kHotStageCount = 4;     // ... a tile's counter stands out at this count (4 of 4096 keys; uniform keys: none does)
-constexpr uint32_t kHotCtlGo = 4, kHotCtlDone = 5, kHotCtlStage = 6, kHotCtlWords = 8;   // hot_ctl beyond kHotCtl*: 2-3 = the tuples S's pass wrote
+constexpr uint32_t kHotStageCount = 4;     // auto mode: a workgroup's counter stands out at this count per tile counted (4 of 4096 keys; uniform keys: none does)
+constexpr uint32_t kHotCtlVotes = 4, kHotCtlWords = 8;   // hot_ctl beyond kHotCtl*: 2-3 = the tuples S's pass wrote, 4 = the sample workgroups that flushed
 constexpr uint32_t kHotListHeavy = 4096, kHotListRest = 12288;   // k_hot_select's LDS lists of counters at or above the threshold
-constexpr uint32_t kHotResolveBlock = 1024;   // k_hot_resolve: a wave per tile of R's tile list
 
 // dynamic LDS of k_hot_select
 __host__ __device__ constexpr size_t hot_select_lds_bytes(uint32_t nb) {
@@ -74,7 +84,7 @@ struct HotArgs {
     unsigned long long* w;      // [nb][kHotPer]
     uint32_t* ctl;          // kHotCtl*
     unsigned long long* rep;    // [kHotCounters] a code that counted into the counter in this join
-    uint32_t staged;        // 1: two sample stages (k_hot_sample phase 1, 2), else one (phase 0)
+    uint32_t staged;        // 1: auto mode, a sample workgroup flushes only if its own counters show skew; 0: it always does
 };
 
 // device words of the state: counters, codes, weights, control words, representatives
@@ -92,34 +102,39 @@ __device__ __forceinline__ uint32_t hot_tile_of(const HotArgs& a, uint32_t i) {
     return static_cast<uint32_t>(static_cast<uint64_t>(i) * a.ntiles / a.nsamp);
 }
 
+// Counters and control words zeroed: only when the state is not known to be
+// clean (k_hot_select leaves it clean for the next join).
 __global__ __launch_bounds__(kHotBlock) void k_hot_clear(HotArgs a) {
     const uint32_t i0 = blockIdx.x * kHotBlock + threadIdx.x, step = gridDim.x * kHotBlock;
     for (uint32_t i = i0; i < kHotCounters; i += step) a.counters[i] = 0;
-    if (i0 < kHotCtlWords) a.ctl[i0] = i0 == kHotCtlGo && !a.staged ? 1u : 0u;
+    if (i0 < kHotCtlWords) a.ctl[i0] = 0;
 }
 
 // Sample tiles counted in LDS (two 16-bit counters per word: a workgroup
-// counts at most kHotTilesPerWg * 4096 keys, so no half carries), then the
-// non-zero counters added to the global ones: the flush is the same number of
-// atomic instructions however many tiles were counted.
-// phase 0: every sample tile, kHotTilesPerWg per workgroup; 1: the first look
-// at tiles 0, 8, 16, .. , one per workgroup (nothing global but the verdict);
-// 2: as 0, if phase 1 said go
+// counts at most kHotTilesPerWg * 4096 keys, so no half carries), kHotTilesPerWg
+// per workgroup. Auto mode (a.staged): the keys of the counters that stand out
+// (kHotStageCount per tile counted) are added up, and unless they are a
+// sixteenth of the keys counted the workgroup returns with nothing written.
+// Else every sampled lane leaves its code in its counter's representative
+// word, the non-zero counters are added to the global ones (the same number
+// of atomic instructions however many tiles were counted) and the workgroup
+// votes. No workgroup waits for another: the selection is the next launch.
 template <int HK>
-__global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a, uint32_t phase) {
+__global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hot_lds[];   // [kHotCounters / 2]
+    __shared__ uint32_t sum;
     const uint32_t tid = threadIdx.x;
-    if (phase == 2 && __hip_atomic_load(&a.ctl[kHotCtlGo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;   // workgroup-uniform
     const uint32_t b = blockIdx.x;
-    const uint32_t s0 = phase == 1 ? b * kHotStage : b * kHotTilesPerWg;
-    const uint32_t s1 = phase == 1 ? s0 + 1 : min(s0 + kHotTilesPerWg, a.nsamp);
+    const uint32_t s0 = b * kHotTilesPerWg;
+    const uint32_t s1 = min(s0 + kHotTilesPerWg, a.nsamp);
     if (s0 >= a.nsamp) return;
     for (uint32_t i = tid; i < kHotCounters / 2; i += kHotBlock) hot_lds[i] = 0;
+    if (tid == 0) sum = 0;
     __syncthreads();
     const longlong2* rel = reinterpret_cast<const longlong2*>(a.rel);
     // every key of the workgroup's tiles requested before the first is used
     constexpr uint32_t I = kHotTile / kHotBlock, K = kHotTilesPerWg * I;
-    int64_t key[K];
+    int64_t key[K];   // the keys, then their codes
     uint32_t have = 0;
 #pragma unroll
     for (uint32_t k = 0; k < K; k++) {
@@ -135,41 +150,32 @@ __global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a, uint32_t ph
         const uint64_t code = hash64<HK>(static_cast<uint64_t>(key[k]), a.f.seed);
         const uint32_t ci = hot_counter_of(code);
         atomicAdd(&hot_lds[ci >> 1], 1u << ((ci & 1u) * 16));
-        if (phase != 1) a.rep[ci] = code;
+        key[k] = static_cast<int64_t>(code);
     }
     __syncthreads();
-    if (phase != 1) {
+    if (a.staged) {   // workgroup-uniform
+        const uint32_t out = kHotStageCount * (s1 - s0);
+        uint32_t m = 0;
         for (uint32_t i = tid; i < kHotCounters / 2; i += kHotBlock) {
-            const uint32_t v = hot_lds[i];
-            if (v & 0xffffu) atomicAdd(&a.counters[2 * i], v & 0xffffu);
-            if (v >> 16) atomicAdd(&a.counters[2 * i + 1], v >> 16);
+            const uint32_t v = hot_lds[i], c0 = v & 0xffffu, c1 = v >> 16;
+            m += (c0 >= out ? c0 : 0u) + (c1 >= out ? c1 : 0u);
         }
-        return;
-    }
-    // the first look: this tile's keys in counters that stand out; the
-    // stage's last workgroup turns the sum into the verdict
-    __shared__ uint32_t sum;
-    if (tid == 0) sum = 0;
-    __syncthreads();
-    uint32_t m = 0;
-    for (uint32_t i = tid; i < kHotCounters / 2; i += kHotBlock) {
-        const uint32_t v = hot_lds[i], c0 = v & 0xffffu, c1 = v >> 16;
-        m += (c0 >= kHotStageCount ? c0 : 0u) + (c1 >= kHotStageCount ? c1 : 0u);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
+        if ((tid & 63) == 0 && m) atomicAdd(&sum, m);
+        __syncthreads();
+        const uint64_t cap = static_cast<uint64_t>(s1 - s0) * kHotTile, keys = a.n < cap ? a.n : cap;
+        if (static_cast<uint64_t>(sum) * 16 < keys) return;   // no skew here: no global trace
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
-    if ((tid & 63) == 0 && m) atomicAdd(&sum, m);
-    __syncthreads();
-    if (tid == 0) {
-        if (sum) atomicAdd(&a.ctl[kHotCtlStage], sum);
-        __threadfence();
-        if (atomicAdd(&a.ctl[kHotCtlDone], 1u) == gridDim.x - 1) {
-            __threadfence();
-            const uint32_t all = atomicAdd(&a.ctl[kHotCtlStage], 0u);
-            const uint64_t cap = static_cast<uint64_t>(gridDim.x) * kHotTile, keys = a.n < cap ? a.n : cap;
-            __hip_atomic_store(&a.ctl[kHotCtlGo], static_cast<uint64_t>(all) * 16 >= keys ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+    for (uint32_t k = 0; k < K; k++)
+        if ((have >> k) & 1u) a.rep[hot_counter_of(static_cast<uint64_t>(key[k]))] = static_cast<unsigned long long>(key[k]);
+    for (uint32_t i = tid; i < kHotCounters / 2; i += kHotBlock) {
+        const uint32_t v = hot_lds[i];
+        if (v & 0xffffu) atomicAdd(&a.counters[2 * i], v & 0xffffu);
+        if (v >> 16) atomicAdd(&a.counters[2 * i + 1], v >> 16);
     }
+    if (tid == 0) atomicAdd(&a.ctl[kHotCtlVotes], 1u);
 }
 
 // The selection, one workgroup: the counters read with coalesced loads, and
@@ -181,17 +187,20 @@ __global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a, uint32_t ph
 // counts. A counter has one representative and a code has one counter, so no
 // code is offered twice. The lists hold four times the ways of the largest
 // table; a counter past their end is dropped as a full set would drop it. Then the table, zero weights and {entries, sampled
-// keys the entries' counters cover} are written out; without a go from the
-// first look that is an empty table.
+// keys the entries' counters cover} are written out; without a vote from the
+// sample that is an empty table at once (nothing was flushed). What the
+// sample wrote is zeroed again for the next join: the counters (when there
+// was a vote; they are read until the last round) and every control word.
 __global__ __launch_bounds__(kHotBlock) void k_hot_select(HotArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long hot_tab[];   // [nb][kHotPer], then the lists
     __shared__ uint32_t s_entries, s_mass, s_scan[kHotBlock / 64];
     const uint32_t tid = threadIdx.x, slots = a.nb * kHotPer;
     uint32_t* hot_list = reinterpret_cast<uint32_t*>(hot_tab + slots);   // [kHotListHeavy + kHotListRest]
+    const uint32_t votes = __hip_atomic_load(&a.ctl[kHotCtlVotes], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (uint32_t i = tid; i < slots; i += kHotBlock) hot_tab[i] = i < kHotPer ? a.e0 : 0ull;
     if (tid == 0) s_entries = s_mass = 0;
     __syncthreads();
-    if (__hip_atomic_load(&a.ctl[kHotCtlGo], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {   // workgroup-uniform
+    if (votes != 0) {   // workgroup-uniform
         // the counters that reached the threshold, compacted into two LDS
         // lists (heavy, the rest: a scan of the threads' numbers of each), so
         // that the rounds below share them evenly: {counter, count} in 16
@@ -256,83 +265,15 @@ __global__ __launch_bounds__(kHotBlock) void k_hot_select(HotArgs a) {
         if (entries) atomicAdd(&s_entries, entries);
         if (mass) atomicAdd(&s_mass, mass);
         __syncthreads();
+#pragma unroll
+        for (uint32_t j = 0; j < V; j++) reinterpret_cast<uint4*>(a.counters)[j * kHotBlock + tid] = make_uint4(0, 0, 0, 0);
     }
     for (uint32_t i = tid; i < slots; i += kHotBlock) {
         a.code[i] = hot_tab[i];
         a.w[i] = 0;
     }
-    if (tid == 0) {
-        a.ctl[kHotCtlEntries] = s_entries;
-        a.ctl[kHotCtlMass] = s_mass;
-    }
-}
-
-// The hot weights resolved against R, after S's pass 1 and its bookkeeping
-// (which clears the count) and after R's pass-1 tile list is built: one
-// workgroup per cluster reads the cluster's entries, returns at once when the
-// table is ignored (the pass's own test) or the cluster's weights are all 0,
-// else scans the cluster's R codes tile by tile through R's pass-1 tile list
-// (any number of tiles and codes: the HBM-table clusters need no case of
-// their own), flags the entries it meets and adds each flagged entry's weight
-// once: a key R holds twice counts once, as in the probe's set test.
-struct HotResolveArgs {
-    const unsigned long long* code;   // [nb][kHotPer]
-    const unsigned long long* w;      // [nb][kHotPer]
-    const uint32_t* ctl;
-    uint32_t min_mass;
-    const uint32_t* rt_base;          // [nb + 1]: R's pass-1 tiles of each cluster
-    const uint32_t* rt_start;         // tile -> first pool slot
-    const uint32_t* rt_cnt;           // tile -> codes
-    const int64_t* r_pool;            // R's chunk pool (codes)
-    unsigned long long* count;
-};
-
-__global__ __launch_bounds__(kHotResolveBlock) void k_hot_resolve(HotResolveArgs a) {
-    __shared__ uint32_t met[kHotPer];
-    const uint32_t d = blockIdx.x, tid = threadIdx.x;
-    if (a.ctl[kHotCtlEntries] == 0 || a.ctl[kHotCtlMass] < a.min_mass) return;   // grid-uniform
-    unsigned long long hc[kHotPer], hw[kHotPer];
-    bool any = false;
-#pragma unroll
-    for (uint32_t e = 0; e < kHotPer; e++) {
-        hc[e] = a.code[static_cast<size_t>(d) * kHotPer + e];
-        hw[e] = a.w[static_cast<size_t>(d) * kHotPer + e];
-        any = any || hw[e] != 0;
-    }
-    if (!any) return;   // workgroup-uniform
-    if (tid < kHotPer) met[tid] = 0;
-    __syncthreads();
-    // a wave per tile (R's pass has 8 shards: most of a cluster's tiles are
-    // partial, a shard's share of its codes), U loads of a lane in flight
-    constexpr uint32_t NW = kHotResolveBlock / 64, U = 8;
-    const uint32_t wave = tid / 64, l = tid % 64;
-    const uint32_t t0 = a.rt_base[d], t1 = a.rt_base[d + 1];
-    for (uint32_t ti = t0 + wave; ti < t1; ti += NW) {
-        const int64_t* src = a.r_pool + a.rt_start[ti];
-        const uint32_t c = a.rt_cnt[ti];
-        for (uint32_t r0 = 0; r0 < c; r0 += U * 64) {
-            unsigned long long v[U];
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) {
-                const uint32_t r = r0 + u * 64 + l;
-                v[u] = static_cast<unsigned long long>(src[r < c ? r : 0]);
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < U; u++) {
-                if (r0 + u * 64 + l >= c) continue;
-#pragma unroll
-                for (uint32_t e = 0; e < kHotPer; e++)
-                    if (v[u] == hc[e] && hw[e] != 0) met[e] = 1;
-            }
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long sum = 0;
-#pragma unroll
-        for (uint32_t e = 0; e < kHotPer; e++) sum += met[e] ? hw[e] : 0ull;
-        if (sum) atomicAdd(a.count, sum);
-    }
+    // (every thread has read the votes: the barrier after the table's clearing)
+    if (tid < kHotCtlWords) a.ctl[tid] = tid == kHotCtlEntries ? s_entries : tid == kHotCtlMass ? s_mass : 0u;
 }
 
 }  // namespace phj

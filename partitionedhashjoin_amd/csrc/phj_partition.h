@@ -142,7 +142,7 @@ struct PassArgs {
     // k_chunk_codes_pipe HOT (phj_hot.h): the hot table of this join's probe
     // side, [nbins][kHotPer] codes and 64-bit weights, its control words
     // (kHotCtl*), the sample mass below which the table is ignored
-    // (hot_count: no pass reads it; k_hot_resolve adds the weights to the count)
+    // (hot_count: no pass reads it; the LDS join adds the weights to the count)
     const unsigned long long* hot_code;
     unsigned long long* hot_w;
     const uint32_t* hot_ctl;
@@ -153,8 +153,8 @@ constexpr int kP1ProfWords = 16;
 // the hot table: every digit has kHotSub sets (chosen by the code's top bit)
 // of kHotWays ways, so a lookup is one 16-B LDS read
 constexpr uint32_t kHotWays = 2, kHotSub = 2, kHotPer = kHotWays * kHotSub;
-#ifndef PHJ_HOT_AGG   // (a measurement build may aggregate the weight adds per wave: DESIGN.md section 3)
-#define PHJ_HOT_AGG 0
+#ifndef PHJ_HOT_FUSE   // S's pass, HOT 1: a code's weight add and rank claim are one LDS atomic (0: two, the A/B leg)
+#define PHJ_HOT_FUSE 1
 #endif
 constexpr uint32_t kHotCtlEntries = 0, kHotCtlMass = 1;   // hot_ctl words: entries, sampled keys they cover
 
@@ -1146,10 +1146,10 @@ __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int h
 // of its digit. 1 (S's pass): a code found there adds 1 to its entry's LDS
 // weight and is neither ranked nor written, so a tile's valid count is the
 // scan's total of kept codes; the workgroup adds its weights to the global
-// ones when it ends (k_hot_resolve then adds the weights of the entries R
+// ones when it ends (the LDS join then adds the weights of the entries R
 // holds to the count). A table with no entries, or covering less than
 // hot_min_mass sampled keys, skips the lookups (workgroup-uniform, and the
-// same test as k_hot_resolve's: they read the same words).
+// same test as the LDS join's: they read the same words).
 template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : BLOCK / 256)))
 void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
@@ -1318,9 +1318,15 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             else hash_all(F0{}, std::false_type{});
             const uint32_t ahead = tile + KPF * slots;
             load(key[kb], ahead < t_end ? ahead : tile);
+            uint32_t hm = 0;        // HOT 1: bit i = item i is a hot code ...
+            uint32_t hew[ITEMS];    // ... of this entry
+            (void)hm, (void)hew;
             if constexpr (HOT != 0) {
 #pragma unroll
-                for (int i = 0; i < ITEMS; i++) keep |= (wbase + i * 64 + lane < cnt ? 1u : 0u) << i;
+                for (int i = 0; i < ITEMS; i++) {
+                    keep |= (wbase + i * 64 + lane < cnt ? 1u : 0u) << i;
+                    hew[i] = 0;
+                }
                 if (hot) {
                     // every set read first, then the compares: no branch per
                     // code (a branch waits for its own LDS read: four round
@@ -1339,33 +1345,39 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                         const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
                         const bool m0 = set[i].x == lo && set[i].y == hi, m1 = set[i].z == lo && set[i].w == hi;
                         const bool m = (m0 || m1) && ((keep >> i) & 1u) != 0;
-                        const uint32_t ew = e[i] + (m0 ? 0u : 1u);
-                        if constexpr (HOT == 1) {
-                            // (a lane without a match adds 0 to a word of its own)
-#if PHJ_HOT_AGG   // measurement build: the lanes sharing the first matching lane's entry add once
-                            const uint64_t act = __ballot(m);
-                            const int leader = act ? __builtin_ctzll(act) : 0;
-                            const uint32_t lew = __builtin_amdgcn_readlane(ew, leader);
-                            const bool same = m && ew == lew;
-                            const uint32_t nsame = static_cast<uint32_t>(__popcll(__ballot(same)));
-                            const bool lead = same && lane == static_cast<uint32_t>(leader);
-                            atomicAdd(lead ? &hwt[lew] : m && !same ? &hwt[ew] : &hown[tid], lead ? nsame : m && !same ? 1u : 0u);
-#else
-                            atomicAdd(m ? &hwt[ew] : &hown[tid], m ? 1u : 0u);
-#endif
-                            keep &= ~((m ? 1u : 0u) << i);
-                        }
+                        hew[i] = e[i] + (m0 ? 0u : 1u);
+                        hm |= (m ? 1u : 0u) << i;
                     }
+                    if constexpr (HOT == 1) keep &= ~hm;
                 }
             }
             if constexpr (HOT == 1) {
-                // (a dropped code claims no rank: 0 added to the lane's own word, not
-                // to its digit's counter, where a hot key's lanes would still queue)
+#if PHJ_HOT_FUSE
+                // one LDS atomic per code: a hot code counts into its entry's
+                // weight, a kept one claims its rank, any other adds 0 to the
+                // lane's own word (not to its digit's counter, where a hot key's
+                // lanes would still queue). Only a kept code's rank is read
+#pragma unroll
+                for (int i = 0; i < ITEMS; i++) {
+                    const bool m = ((hm >> i) & 1u) != 0, k = ((keep >> i) & 1u) != 0;
+                    rank[i] = atomicAdd(m ? &hwt[hew[i]] : k ? &crow[dig[i]] : &hown[tid], m || k ? 1u : 0u);
+                }
+#else
+                // the weight add (a lane without a match adds 0 to a word of its
+                // own), then the rank claim (a dropped code claims none)
+                if (hot) {
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) {
+                        const bool m = ((hm >> i) & 1u) != 0;
+                        atomicAdd(m ? &hwt[hew[i]] : &hown[tid], m ? 1u : 0u);
+                    }
+                }
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
                     const bool k = ((keep >> i) & 1u) != 0;
                     rank[i] = atomicAdd(k ? &crow[dig[i]] : &hown[tid], k ? 1u : 0u);
                 }
+#endif
             } else {
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) rank[i] = atomicAdd(&crow[dig[i]], wbase + i * 64 + lane < cnt ? 1u : 0u);

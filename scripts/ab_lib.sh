@@ -6,7 +6,8 @@
 #  `make build/libphj_res1.so HIPDEFS=-DPHJ_PIPE_RES=1`-style variants the same way; PHJ_LIB selects it;
 #  `make build/libphj_nopreagg.so HIPDEFS=-DPHJ_PREAGG=0`: without the hot-key pre-aggregation, csrc/phj_hot.h;
 #  `make build/libphj_late.so HIPDEFS=-DPHJ_HOT_EARLY_R=0`: R's chain after S's pass 1, not beside the hot-key prologue;
-#  `HIPDEFS=-DPHJ_HOT_FREE_CUS=N`: the CUs per XCD R's pass 1 leaves to the prologue)
+#  `HIPDEFS=-DPHJ_HOT_FREE_CUS=N`: the CUs per XCD R's pass 1 leaves to the prologue;
+#  `make build/libphj_nofuse.so HIPDEFS=-DPHJ_HOT_FUSE=0`: S's pass with the weight add and the rank claim as two LDS atomics)
 # The JSON lines go to $OUT (default ab_out/).
 set -o pipefail
 OUT=${OUT:-ab_out}
