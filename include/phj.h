@@ -256,6 +256,59 @@ int phj_relation_generate_zipf(phj_ctx *ctx, int side, uint64_t n, double alpha,
 /* Count tuples of the bound relation with lo <= id <= hi (device reduction). */
 int phj_relation_count_in_range(phj_ctx *ctx, int side, int64_t lo, int64_t hi, uint64_t *count);
 
+/* ---- relations bound as columns ----
+ * Replaces nothing in the reference, whose Table<Tuple> is an array of tuples.
+ * A caller that keeps a relation as a key column and a payload column (torch
+ * tensors, Arrow, a dataframe, this library's own partitioned views) binds the
+ * two columns instead of interleaving them, and a caller that only wants the
+ * count binds the key column alone.
+ *  - Single-device contexts only: a group or rank context returns
+ *    PHJ_ERR_STATE ("single-device contexts only") from all five calls.
+ *  - Columns need 8-byte alignment and nothing more; the size limits are those
+ *    of a tuple relation. Binding either layout on a side replaces the other.
+ *  - phj_join's counting LDS join (PHJ_PATH_LDS_JOIN) in its default schedule
+ *    reads the key column itself: 8 B per tuple in pass 1 instead of the 16-B
+ *    tuple, no copy made, the payload column never touched.
+ *  - Every other call (phj_join on its other paths, phj_join_materialize,
+ *    phj_join_inner[_count], phj_join_rows[_count], phj_join_aggregate,
+ *    phj_partition, phj_probe_pass1 off the native pass) packs the side once
+ *    into a ctx-owned tuple buffer and runs on that copy as on a tuple
+ *    relation. The copy stays until the side is rebound and DOUBLES that
+ *    side's footprint (16 B per tuple beside the columns). The call that packs
+ *    lists the timer `S.pack` / `R.pack` (32 B per tuple); later calls do not.
+ *  - A key column alone packs with payload 0 for the calls that never look at
+ *    payloads (phj_join, phj_join_inner_count, phj_join_rows_count). A call
+ *    whose result holds payloads or sums of them (phj_join_materialize,
+ *    phj_join_inner, phj_join_rows, phj_join_aggregate) returns PHJ_ERR_STATE
+ *    ("payload column not bound") before any launch.
+ *  - On a side bound as columns phj_relation_device_ptr returns NULL with *n =
+ *    the rows, phj_relation_download writes tuples (payload 0 without a payload
+ *    column), phj_relation_count_in_range counts over the key column. */
+#define PHJ_LAYOUT_TUPLES  0
+#define PHJ_LAYOUT_COLUMNS 1
+typedef struct phj_relation_info {   /* 24 B */
+    uint64_t n;
+    uint32_t layout;        /* PHJ_LAYOUT_* of the bound relation */
+    uint32_t has_payloads;  /* 0: a key column alone */
+    uint32_t packed;        /* 1: the context holds a tuple copy it packed from the columns */
+    uint32_t owned;         /* 1: the columns (or tuples) are context-owned memory */
+} phj_relation_info;
+/* Copy host columns to ctx-owned device memory (H2D, synchronous); payloads may be NULL. */
+int phj_relation_upload_columns(phj_ctx *ctx, int side, const int64_t *keys, const int64_t *payloads,
+                                uint64_t n);
+/* Borrow device columns (the caller keeps them alive while the ctx uses them); dev_payloads may be NULL. */
+int phj_relation_bind_columns(phj_ctx *ctx, int side, const int64_t *dev_keys, const int64_t *dev_payloads,
+                              uint64_t n);
+/* Split the bound tuple relation into ctx-owned columns on the device and make
+ * them the bound relation (with_payloads == 0: the keys alone), e.g. after
+ * phj_relation_generate_*. On a side already bound as columns it does nothing,
+ * except that with_payloads == 0 drops the payload column. */
+int phj_relation_to_columns(phj_ctx *ctx, int side, int with_payloads);
+/* Device pointers of a columnar binding (*payloads NULL for a key column
+ * alone); for a tuple binding both NULL. *n = the rows either way. */
+int phj_relation_columns(phj_ctx *ctx, int side, const int64_t **keys, const int64_t **payloads, uint64_t *n);
+int phj_relation_info_get(phj_ctx *ctx, int side, phj_relation_info *out);
+
 /* ---- the join (HashJoiner::Run) ---- */
 /* Synchronous: partition (radix) / build / probe on the device, count back on the host. */
 int phj_join(phj_ctx *ctx, const phj_join_params *p, phj_join_result *r);

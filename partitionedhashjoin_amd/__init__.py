@@ -18,14 +18,15 @@ from ._capi import (AGG_GROUPS, AGG_MATCHED_ONLY, ALGO_NO_PARTITIONING, ALGO_RAD
                     HASH_MURMUR3, HASH_XXH3, INNER, NULL_PAYLOAD, PATH_CODE_TABLES, PATH_LDS_JOIN,
                     PATH_NO_PARTITIONING, PATH_PARTITIONED, PROBE_ANTI, PROBE_OUTER, ROWS_BUILD_ONLY, ROWS_PAIRS,
                     ROWS_PROBE_ONLY, SIDE_BUILD, SIDE_PROBE, GroupRow, JoinParams, JoinResult, JoinTotals, Partitioned,
-                    PhjError, RowCounts)
+                    PhjError, RowCounts, LAYOUT_TUPLES, LAYOUT_COLUMNS, RelationInfo)
 
 __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_JOIN", "PATH_CODE_TABLES",
            "PATH_PARTITIONED", "PATH_NO_PARTITIONING", "count_contribution", "count_verdict", "comm_unique_id", "CTX_EXCHANGE", "CTX_LOCAL", "radix_params", "nopart_params", "JoinParams", "JoinResult",
            "Partitioned", "PhjError", "ALGO_RADIX", "ALGO_NO_PARTITIONING", "HASH_XXH3",
            "HASH_MURMUR3", "SIDE_BUILD", "SIDE_PROBE", "DEFAULT_SEED", "RowCounts", "ROWS_PAIRS", "ROWS_PROBE_ONLY",
            "ROWS_BUILD_ONLY", "INNER", "PROBE_OUTER", "BUILD_OUTER", "FULL_OUTER", "PROBE_ANTI", "BUILD_ANTI",
-           "NULL_PAYLOAD", "JoinTotals", "GroupRow", "AGG_GROUPS", "AGG_MATCHED_ONLY"]
+           "NULL_PAYLOAD", "JoinTotals", "GroupRow", "AGG_GROUPS", "AGG_MATCHED_ONLY",
+           "RelationInfo", "LAYOUT_TUPLES", "LAYOUT_COLUMNS"]
 
 DEFAULT_SEED = 0x9E3779B97F4A7C15
 PART_STABLE = 0x1   # include/phj.h PHJ_PART_STABLE
@@ -219,6 +220,46 @@ class Context:
     def bind_device(self, side: int, ptr: int, n: int, keepalive=None):
         self._keep[side] = keepalive
         self._check(self._L.phj_relation_bind_device(self._h, side, C.c_void_p(ptr), n))
+
+    def upload_columns(self, side: int, keys, payloads=None):
+        """phj_relation_upload_columns: bind host columns (int64 key column and,
+        unless None, a payload column of the same length) as the relation of
+        `side`, copied to context-owned device memory."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        assert keys.ndim == 1
+        pp = None
+        if payloads is not None:
+            payloads = np.ascontiguousarray(payloads, dtype=np.int64)
+            assert payloads.shape == keys.shape
+            pp = payloads.ctypes.data_as(C.c_void_p)
+        self._keep[side] = None
+        self._check(self._L.phj_relation_upload_columns(self._h, side, keys.ctypes.data_as(C.c_void_p), pp,
+                                                        keys.shape[0]))
+
+    def bind_columns(self, side: int, keys_ptr: int, payloads_ptr: int | None, n: int, keepalive=None):
+        """phj_relation_bind_columns: borrow device columns (8-byte aligned
+        addresses, e.g. two torch tensors' data_ptr(); payloads_ptr None or 0:
+        the key column alone). `keepalive` is held while they are bound."""
+        self._keep[side] = keepalive
+        self._check(self._L.phj_relation_bind_columns(self._h, side, C.c_void_p(keys_ptr),
+                                                      C.c_void_p(payloads_ptr or 0), n))
+
+    def to_columns(self, side: int, payloads: bool = True):
+        """phj_relation_to_columns: split the bound tuple relation into
+        context-owned columns on the device (payloads=False: the keys alone)."""
+        self._check(self._L.phj_relation_to_columns(self._h, side, 1 if payloads else 0))
+
+    def columns_ptr(self, side: int):
+        """(keys_ptr, payloads_ptr, n) of a columnar binding; the pointers are
+        None for a tuple binding (and payloads_ptr for a key column alone)."""
+        k, p, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._check(self._L.phj_relation_columns(self._h, side, C.byref(k), C.byref(p), C.byref(n)))
+        return k.value, p.value, n.value
+
+    def relation_info(self, side: int) -> RelationInfo:
+        info = RelationInfo()
+        self._check(self._L.phj_relation_info_get(self._h, side, C.byref(info)))
+        return info
 
     def relation_ptr(self, side: int):
         n = C.c_uint64()

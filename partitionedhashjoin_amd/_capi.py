@@ -42,6 +42,8 @@ EXPORTED = [
     "phj_exchange_layout", "phj_count_contribution", "phj_count_verdict", "phj_join_path",
     "phj_join_inner_count", "phj_join_inner", "phj_join_rows_count", "phj_join_rows",
     "phj_debug_preagg", "phj_join_aggregate", "phj_group_rows", "phj_group_download",
+    "phj_relation_upload_columns", "phj_relation_bind_columns", "phj_relation_to_columns",
+    "phj_relation_columns", "phj_relation_info_get",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
@@ -53,6 +55,7 @@ ROWS_PAIRS, ROWS_PROBE_ONLY, ROWS_BUILD_ONLY = 0x1, 0x2, 0x4
 INNER, PROBE_OUTER, BUILD_OUTER, FULL_OUTER, PROBE_ANTI, BUILD_ANTI = 1, 3, 5, 7, 2, 4
 NULL_PAYLOAD = -2**63   # the default marker for the missing side (INT64_MIN)
 AGG_GROUPS, AGG_MATCHED_ONLY = 0x1, 0x2   # phj_join_aggregate's flags
+LAYOUT_TUPLES, LAYOUT_COLUMNS = 0, 1   # phj_relation_info.layout
 
 
 class Tuple(C.Structure):
@@ -113,6 +116,17 @@ class GroupRow(C.Structure):
     _fields_ = [("id", C.c_int64), ("payload_a", C.c_int64), ("partners", C.c_uint64), ("sum_b", C.c_int64)]
 
 
+class RelationInfo(C.Structure):
+    """phj_relation_info: how a side is bound (tuples or columns; whether a
+    payload column is bound; whether the context holds a packed tuple copy)."""
+    _fields_ = [("n", C.c_uint64), ("layout", C.c_uint32), ("has_payloads", C.c_uint32),
+                ("packed", C.c_uint32), ("owned", C.c_uint32)]
+
+    def as_dict(self):
+        return {"n": self.n, "layout": self.layout, "has_payloads": self.has_payloads,
+                "packed": self.packed, "owned": self.owned}
+
+
 class Partitioned(C.Structure):
     _fields_ = [("keys", C.c_void_p), ("payloads", C.c_void_p), ("bounds", C.c_void_p),
                 ("n", C.c_uint64), ("num_partitions", C.c_uint32), ("reserved", C.c_uint32)]
@@ -159,6 +173,11 @@ def load():
         "phj_relation_bind_device": (i, [P, i, P, u64]),
         "phj_relation_device_ptr": (P, [P, i, C.POINTER(u64)]),
         "phj_relation_download": (i, [P, i, P, u64]),
+        "phj_relation_upload_columns": (i, [P, i, P, P, u64]),
+        "phj_relation_bind_columns": (i, [P, i, P, P, u64]),
+        "phj_relation_to_columns": (i, [P, i, i]),
+        "phj_relation_columns": (i, [P, i, C.POINTER(P), C.POINTER(P), C.POINTER(u64)]),
+        "phj_relation_info_get": (i, [P, i, C.POINTER(RelationInfo)]),
         "phj_relation_generate_sequential": (i, [P, i, u64, i64, u64]),
         "phj_relation_generate_zipf": (i, [P, i, u64, d, i64, i64, u64, u64]),
         "phj_relation_count_in_range": (i, [P, i, i64, i64, C.POINTER(u64)]),
@@ -193,7 +212,13 @@ def load():
         "phj_group_download": (i, [P, P, u64]),
     }
     for name, (res, args) in sig.items():
-        f = getattr(L, name)
+        f = getattr(L, name, None)
+        if f is None:
+            # only an A/B build of older sources (PHJ_LIB) may lack a symbol:
+            # a call it lacks then fails at the call
+            if os.environ.get("PHJ_LIB"):
+                continue
+            raise ImportError(f"{LIB_PATH} does not export {name}: rebuild it (`make`)")
         f.restype = res
         f.argtypes = args
     _lib = L

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <string>
 #include <type_traits>
@@ -36,6 +37,13 @@
 #endif
 #ifndef PHJ_HOT_FREE_CUS
 #define PHJ_HOT_FREE_CUS 6
+#endif
+// The column form of the 1024 x 4 code pass (a relation bound as columns): 0 =
+// 8 B per lane and load; 1 = 16 B, two neighbouring keys (the A/B leg,
+// scripts/ab_lib.sh: measured level with 8 B, DESIGN.md "Columnar relations";
+// a column of one key takes the 8-B form).
+#ifndef PHJ_COL_LOAD16
+#define PHJ_COL_LOAD16 0
 #endif
 #ifndef PHJ_P1_PROF
 #define PHJ_P1_PROF 0
@@ -139,6 +147,14 @@ struct SideState {
     const phj_tuple* rel = nullptr;
     uint64_t n = 0;
     DevBuf owned;
+    // bound as columns (phj_relation_bind_columns ...): the key column and the
+    // payload column (null: keys alone), borrowed or in ck / cp. rel is then
+    // null until a call without a column form packs the tuple copy `pack`
+    // (need_tuples), kept until the side is rebound
+    bool columns = false, cols_owned = false, packed = false;
+    const int64_t* ckeys = nullptr;
+    const int64_t* cpays = nullptr;
+    DevBuf ck, cp, pack;
     DevBuf kA, pA, kB, pB;
     DevBuf hist1, hist2, bounds1, tbase2, tseg2, bounds, partials;
     DevBuf dig;           // pass-2 digit column written by pass 1
@@ -248,6 +264,7 @@ struct phj_ctx {
     // the chunked pass 1 launched next leaves free
     hipEvent_t hot_fork = nullptr, hot_join = nullptr;
     uint32_t p1_free_cus = 0;
+    bool p1_cols = false;   // the chunked pass 1 launched next reads a key column (partition_state, cols_native)
 };
 
 namespace {
@@ -678,8 +695,24 @@ int scan_u32(phj_ctx* c, uint32_t* data, uint32_t len, uint32_t narrays, uint32_
 // The pipelined code pass in 1024 x 4 workgroups: KPF tiles of keys in
 // flight (S: 2, measured 1.08 -> 1.05 ms at C2; R: 1); a measurement build
 // (-DPHJ_P1_PROF=1, scripts/ab_lib.sh) runs S's pass in the phase-clock form.
+// cols: the relation is a key column (k_chunk_codes_pipe COLS 1 / 2, one digit
+// per thread only: cols_native).
 template <int HK, int DPT>
-const void* pipe1024(int kpf, bool hot = false) {
+const void* pipe1024(int kpf, bool hot = false, int cols = 0) {
+    if constexpr (DPT == 1 && PHJ_COL_LOAD16 != 0) {
+        if (cols == 2) {
+            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, PHJ_PREAGG != 0 ? 1 : 0, 2>);
+            if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 0, 2>);
+            return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 0, 2>);
+        }
+    }
+    if constexpr (DPT == 1) {
+        if (cols != 0) {
+            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, PHJ_PREAGG != 0 ? 1 : 0, 1>);
+            if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 0, 1>);
+            return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 0, 1>);
+        }
+    }
     if constexpr (DPT == 1 && PHJ_PREAGG != 0) {   // the HOT form (phj_hot.h): S's pass counts the hot codes' weights
         if (hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 1>);
     }
@@ -732,7 +765,8 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
         if (a.chunk_cursor == c->p1_cleared) c->p1_cleared = nullptr;   // cleared by the kernel before it
         else if (!zeroed) PHJ_HIP(c, hipMemsetAsync(a.chunk_cursor, 0, chunk_state_bytes(a.nbins), c->ks));
         c->since_ev++;
-        const uint64_t sbytes = n * (a.keys_only ? 24 : 32) + (a.out_dig ? n * (a.dig_wide ? 2 : 1) : 0);
+        // (a key column, c->p1_cols: 8 B read per tuple, not the 16-B tuple)
+        const uint64_t sbytes = n * (a.keys_only ? 24 : 32) - (c->p1_cols ? n * 8 : 0) + (a.out_dig ? n * (a.dig_wide ? 2 : 1) : 0);
         PHJ_TRY(timer_begin(c, sname.c_str(), sbytes));
         if constexpr (IN_AOS && OUT_AOS && ITEMS <= 8) {
             // persistent: as many workgroups per shard as fit the chip at once
@@ -746,6 +780,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                                : a.keys_only ? chunk_codes_lds_bytes(T, a.nbins) : sc_lds;
             const void* kfn = nullptr;
             int kblock = BLOCK;
+            bool cols_form = false;   // the kernel chosen reads a key column
             // keys only, written as hash codes (the on-chip probe): k_chunk_codes;
             // whole tuples: VAR 3, LDS-atomic ranking, 16-B LDS entries (phj_partition.h)
             // (more digits than threads: the cluster plans, 512 x 4096 only)
@@ -759,9 +794,12 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                         // its own in rocprof summaries (S's is the roofline kernel)
                         const int kpf = is_r ? 1 : 2;
                         if (hot && dpt == 4) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation: more digits than threads");
+                        if (c->p1_cols && dpt == 4) return set_err(c, PHJ_ERR_STATE, "key column: more digits than threads");
+                        const int cols = !c->p1_cols ? 0 : PHJ_COL_LOAD16 != 0 && n >= 2 ? 2 : 1;
+                        cols_form = cols != 0;
                         kfn = with_hash(hk, [&](auto h) {
                             constexpr int HK = decltype(h)::value;
-                            return dpt == 4 ? pipe1024<HK, 2>(kpf) : pipe1024<HK, 1>(kpf, hot);
+                            return dpt == 4 ? pipe1024<HK, 2>(kpf) : pipe1024<HK, 1>(kpf, hot, cols);
                         });
                     } else if (hot) {
                         return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs the 1024-thread code pass");
@@ -791,6 +829,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                 kfn = with_hash(hk, [](auto h) {
                     return reinterpret_cast<const void*>(&k_scatter_chunked<BLOCK, ITEMS, decltype(h)::value, 3>);
                 });
+            if (c->p1_cols && !cols_form) return set_err(c, PHJ_ERR_STATE, "key column: this code pass has no column form");
             // workgroups per CU: what the LDS and the kernel's registers allow
             // (cached per kernel and LDS size; one cache per worker thread)
             const int occ = std::max(1, occupancy(kfn, kblock, lds));
@@ -941,10 +980,24 @@ bool chunked_pass1(const phj_ctx* c, const Plan& pl, uint64_t n64, bool ko) {
     return true;
 }
 
+// A side bound as columns whose keys-only pass 1 under plan pl is the 1024 x 4
+// pipelined code pass with one digit per thread (the counting LDS join's
+// default schedule): that pass, and the hot-key sample, read the key column
+// itself (k_chunk_codes_pipe COLS, k_hot_sample COLS) and no tuple copy is
+// made. Every other pass runs on the packed copy (need_tuples).
+bool cols_native(const phj_ctx* c, const SideState& S, const Plan& pl, bool is_r) {
+    if (!S.columns || S.n == 0) return false;
+    if (!c->tune.p1_pipe || c->tune.p1_block != 1024 || pl.nb1 > 1024 || (is_r && !c->tune.r_chunk)) return false;
+    const TileShape sh = tile_shape(c, pl.nb1);
+    return sh.block == 512 && sh.tile == 4096 && chunked_pass1(c, pl, S.n, true);
+}
+
 int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, bool p1_only,
                     unsigned long long* zero = nullptr, uint32_t max_shards = kShards) {
     c->scan_scratch = &S.partials;
-    if (!S.rel && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    if (!S.rel && !S.columns && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    const bool cols = p1_only && cols_native(c, S, pl, &S == &c->side[PHJ_SIDE_BUILD]);
+    if (!S.rel && !cols && !c->dry && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation bound as columns: no tuple copy was packed for this pass");
     const uint64_t n64 = S.n;
     if (n64 >= (1ull << 32) - 2 * 4096) return set_err(c, PHJ_ERR_RANGE, "relation above 2^32 tuples per device");
     const uint32_t n = static_cast<uint32_t>(n64);
@@ -1022,9 +1075,9 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
         if (pl.npass == 2 && n) PHJ_TRY(scan_u32(c, nullptr, nt2 * pl.nb2, 1, nt2 * pl.nb2, c->scan_scratch));
         return PHJ_OK;
     }
-    // pass 1: AoS relation -> SoA columns A
+    // pass 1: AoS relation -> SoA columns A (cols: the key column -> codes)
     PassArgs a{};
-    a.in_keys = reinterpret_cast<const int64_t*>(S.rel);
+    a.in_keys = cols ? S.ckeys : reinterpret_cast<const int64_t*>(S.rel);
     a.out_keys = static_cast<int64_t*>(S.kA.p);
     a.out_pays = static_cast<int64_t*>(S.pA.p);
     a.hist = static_cast<uint32_t*>(S.hist1.p);
@@ -1064,7 +1117,10 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
         kept = reinterpret_cast<unsigned long long*>(const_cast<uint32_t*>(a.hot_ctl) + 2);
     }
     uint32_t* tb2 = pl.npass == 2 ? static_cast<uint32_t*>(S.tbase2.p) : nullptr;
-    PHJ_TRY(launch_pass(c, pl.hk, true, p1_aos, a, nt1, std::string(tag) + ".p1", n, nt1 * pl.nb1));
+    c->p1_cols = cols;
+    const int rc1 = launch_pass(c, pl.hk, true, p1_aos, a, nt1, std::string(tag) + ".p1", n, nt1 * pl.nb1);
+    c->p1_cols = false;
+    PHJ_TRY(rc1);
     if (chunked) {
         uint4* clr = nullptr;   // another pass's chunk state, cleared here (c->p1_clear)
         if (c->p1_clear) {
@@ -1180,10 +1236,11 @@ bool hot_wanted(const phj_ctx* c, const Plan& cpl, uint64_t nS, uint64_t nR) {
 // code pass of this join then takes its HOT form (c->hot_on). Forced
 // mode (phj_debug_preagg) takes the lowest threshold and any coverage.
 int hot_begin(phj_ctx* c, const Plan& cpl, const SideState& S) {
+    const bool cols = cols_native(c, S, cpl, false);   // the sample reads the key column
     PHJ_TRY(ensure(c, c->hot, hot_state_bytes(cpl.nb1)));
     const bool forced = c->hot_mode == 2;
     HotArgs h{};
-    h.rel = reinterpret_cast<const int64_t*>(S.rel);
+    h.rel = cols ? S.ckeys : reinterpret_cast<const int64_t*>(S.rel);
     h.n = static_cast<uint32_t>(S.n);
     h.ntiles = (h.n + kHotTile - 1) / kHotTile;
     h.nsamp = std::min(kHotTiles, h.ntiles);
@@ -1201,8 +1258,11 @@ int hot_begin(phj_ctx* c, const Plan& cpl, const SideState& S) {
     c->hot_n = S.n;
     // no timer events under PHJ_LEAN_TIMERS (each one between two kernels costs ~4 us)
     const bool timed = !c->lean_timers;
-    if (timed) PHJ_TRY(timer_begin(c, "S.hot", 1ull * h.nsamp * kHotTile * 16));
-    const void* ksample = with_hash(cpl.hk, [](auto hh) { return reinterpret_cast<const void*>(&k_hot_sample<decltype(hh)::value>); });
+    if (timed) PHJ_TRY(timer_begin(c, "S.hot", 1ull * h.nsamp * kHotTile * (cols ? 8 : 16)));
+    const void* ksample = with_hash(cpl.hk, [&](auto hh) {
+        constexpr int HK = decltype(hh)::value;
+        return cols ? reinterpret_cast<const void*>(&k_hot_sample<HK, true>) : reinterpret_cast<const void*>(&k_hot_sample<HK>);
+    });
     // auto mode: a sample workgroup whose own tiles show no skew writes nothing
     h.staged = !forced && h.nsamp == kHotTiles ? 1u : 0u;
     // the counters and control words: left zero by the last join's selection,
@@ -1476,7 +1536,8 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
 int partition_build(phj_ctx* c, const Plan& pl, int64_t* out, uint32_t* bounds) {
     SideState& S = c->side[PHJ_SIDE_BUILD];
     c->scan_scratch = &S.partials;
-    if (!S.rel && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    if (!S.rel && !S.columns && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    if (!S.rel && !c->dry && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation bound as columns: no tuple copy was packed for this pass");
     if (S.n >= (1ull << 32) - 2 * 4096) return set_err(c, PHJ_ERR_RANGE, "relation above 2^32 tuples per device");
     constexpr int BLOCK = 512, ITEMS = 8, T = BLOCK * ITEMS;
     const uint32_t n = static_cast<uint32_t>(S.n), nb = pl.nb1, P = pl.Ppad;
@@ -2100,6 +2161,45 @@ void drop_relation(phj_ctx* c, int side) {
     S.rel = nullptr;
     S.n = 0;
     S.partitioned = false;
+    // (a columnar binding and its packed copy go with it; the buffers stay, grow-only)
+    S.columns = S.cols_owned = S.packed = false;
+    S.ckeys = S.cpays = nullptr;
+}
+
+// The calls without a column form run on tuples: a side bound as columns is
+// packed once into a ctx-owned tuple buffer (k_pack_columns; payload 0 for a
+// key column alone) that stays until the side is rebound, and S.rel names it.
+// The call that packs records it as `S.pack` / `R.pack`, 16 B read and 16 B
+// written per tuple. need_pay: the call's result holds payloads, so a key
+// column alone is refused before anything is launched. phj_prepare (dry) only
+// sizes the buffer.
+int need_tuples(phj_ctx* c, int side, bool need_pay, const char* what) {
+    SideState& S = c->side[side];
+    if (!S.columns) return PHJ_OK;
+    if (need_pay && !S.cpays && S.n > 0)
+        return set_err(c, PHJ_ERR_STATE, std::string(what) + ": payload column not bound on the " +
+                                             (side == PHJ_SIDE_BUILD ? "build" : "probe") + " side");
+    if (S.packed || S.n == 0) return PHJ_OK;
+    PHJ_TRY(ensure(c, S.pack, S.n * sizeof(phj_tuple)));
+    if (c->dry) return PHJ_OK;
+    PHJ_TRY(timer_begin(c, side == PHJ_SIDE_BUILD ? "R.pack" : "S.pack", S.n * 32));
+    const uint32_t g = static_cast<uint32_t>(std::min<uint64_t>((S.n + kBlock - 1) / kBlock, 65536));
+    hipLaunchKernelGGL(k_pack_columns, dim3(g), dim3(kBlock), 0, c->ks, S.ckeys, S.cpays, S.n, static_cast<longlong2*>(S.pack.p));
+    PHJ_LAUNCHED(c, "k_pack_columns");
+    PHJ_TRY(timer_end(c));
+    S.rel = static_cast<const phj_tuple*>(S.pack.p);
+    S.packed = true;
+    return PHJ_OK;
+}
+
+// Both sides; the payload check of both comes before either is packed.
+int need_tuples_both(phj_ctx* c, bool need_pay, const char* what) {
+    for (int side : {PHJ_SIDE_BUILD, PHJ_SIDE_PROBE}) {
+        const SideState& S = c->side[side];
+        if (need_pay && S.columns && !S.cpays && S.n > 0) return need_tuples(c, side, true, what);
+    }
+    PHJ_TRY(need_tuples(c, PHJ_SIDE_BUILD, need_pay, what));
+    return need_tuples(c, PHJ_SIDE_PROBE, need_pay, what);
 }
 
 uint64_t partition_bytes(const Plan& pl, uint64_t n) {
@@ -2379,6 +2479,7 @@ int join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool em
     if (emit) c->mat_n = 0;
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    PHJ_TRY(need_tuples_both(c, emit, what));   // (sides bound as columns)
     // an empty side joins to nothing (no table to build, no pass to run)
     if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0) return PHJ_OK;
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) PHJ_TRY(join_nopart_inner(c, p, r, emit));
@@ -2595,6 +2696,7 @@ int join_aggregate(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_joi
     c->agg_n = 0;
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    PHJ_TRY(need_tuples_both(c, true, what));   // (sides bound as columns)
     const uint64_t nR = c->side[PHJ_SIDE_BUILD].n, nS = c->side[PHJ_SIDE_PROBE].n;
     // an empty side joins to nothing (no table to build, no pass to run)
     if (nR == 0 || nS == 0) {
@@ -2901,6 +3003,7 @@ int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t nu
     if (emit) c->mat_n = 0;
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    PHJ_TRY(need_tuples_both(c, emit, what));   // (sides bound as columns)
     // decided here: np_build refuses an empty build side, and no table or
     // partition is needed to know that the other side has no partner
     if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0)
@@ -3099,7 +3202,7 @@ void phj_ctx_destroy(phj_ctx* c) {
     if (c->count_host) (void)hipHostFree(c->count_host);
     if (c->count_pin) (void)hipHostFree(c->count_pin);
     for (SideState& S : c->side) {
-        for (DevBuf* b : {&S.owned, &S.kA, &S.pA, &S.kB, &S.pB, &S.hist1, &S.hist2, &S.bounds1, &S.tbase2,
+        for (DevBuf* b : {&S.owned, &S.ck, &S.cp, &S.pack, &S.kA, &S.pA, &S.kB, &S.pB, &S.hist1, &S.hist2, &S.bounds1, &S.tbase2,
                           &S.bounds, &S.partials, &S.tseg2, &S.dig, &S.ccur, &S.ctab, &S.tstart, &S.csink})
             free_buf(*b);
     }
@@ -3192,6 +3295,7 @@ const phj_tuple* phj_relation_device_ptr(phj_ctx* c, int side, uint64_t* n) {
         return nullptr;
     }
     if (n) *n = c->side[side].n;
+    if (c->side[side].columns) return nullptr;   // (phj_relation_columns serves a columnar binding)
     return c->side[side].rel;
 }
 
@@ -3201,10 +3305,124 @@ int phj_relation_download(phj_ctx* c, int side, phj_tuple* host, uint64_t n) {
     SideState& S = c->side[side];
     if (n > S.n) return set_err(c, PHJ_ERR_INVALID, "download larger than the relation");
     PHJ_HIP(c, hipSetDevice(c->device));
+    if (n && S.columns && !S.packed) {   // the columns copied back and interleaved on the host (payload 0 without a payload column)
+        if (!host) return set_err(c, PHJ_ERR_INVALID, "null destination");
+        std::vector<int64_t> col;
+        try {
+            col.resize(n);
+        } catch (const std::exception&) {
+            return set_err(c, PHJ_ERR_NOMEM, "no host memory to stage a column of " + std::to_string(n) + " keys");
+        }
+        for (int f = 0; f < 2; f++) {
+            const int64_t* src = f == 0 ? S.ckeys : S.cpays;
+            if (src) {
+                PHJ_HIP(c, hipMemcpyAsync(col.data(), src, n * 8, hipMemcpyDeviceToHost, c->ks));
+                PHJ_HIP(c, hipStreamSynchronize(c->ks));
+            }
+            for (uint64_t i = 0; i < n; i++) (f == 0 ? host[i].id : host[i].payload) = src ? col[i] : 0;
+        }
+        return PHJ_OK;
+    }
     if (n) {
         PHJ_HIP(c, hipMemcpyAsync(host, S.rel, n * sizeof(phj_tuple), hipMemcpyDeviceToHost, c->ks));
         PHJ_HIP(c, hipStreamSynchronize(c->ks));
     }
+    return PHJ_OK;
+}
+
+// ---- relations bound as columns ----
+static_assert(sizeof(phj_relation_info) == 24, "phj_relation_info layout");
+
+// The side's binding replaced by the columns k / p (p null: keys alone).
+static void bind_columns_state(phj_ctx* c, int side, const int64_t* k, const int64_t* p, uint64_t n, bool owned) {
+    drop_relation(c, side);
+    SideState& S = c->side[side];
+    S.columns = true;
+    S.cols_owned = owned;
+    S.ckeys = k;
+    S.cpays = p;
+    S.n = n;
+    c->hot_clean = nullptr;   // the next hot-key prologue starts from cleared counters
+}
+
+static int columns_guard(phj_ctx* c, int side, const char* what) {
+    PHJ_TRY(check_side(c, side));
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    return PHJ_OK;
+}
+
+int phj_relation_upload_columns(phj_ctx* c, int side, const int64_t* keys, const int64_t* payloads, uint64_t n) {
+    PHJ_TRY(columns_guard(c, side, "phj_relation_upload_columns"));
+    if (n && !keys) return set_err(c, PHJ_ERR_INVALID, "null host key column");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    SideState& S = c->side[side];
+    drop_relation(c, side);
+    PHJ_TRY(ensure(c, S.ck, n * 8));
+    if (payloads) PHJ_TRY(ensure(c, S.cp, n * 8));
+    if (n) {
+        PHJ_HIP(c, hipMemcpyAsync(S.ck.p, keys, n * 8, hipMemcpyHostToDevice, c->ks));
+        if (payloads) PHJ_HIP(c, hipMemcpyAsync(S.cp.p, payloads, n * 8, hipMemcpyHostToDevice, c->ks));
+        PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    }
+    bind_columns_state(c, side, static_cast<const int64_t*>(S.ck.p), payloads ? static_cast<const int64_t*>(S.cp.p) : nullptr, n, true);
+    return PHJ_OK;
+}
+
+int phj_relation_bind_columns(phj_ctx* c, int side, const int64_t* dev_keys, const int64_t* dev_payloads, uint64_t n) {
+    PHJ_TRY(columns_guard(c, side, "phj_relation_bind_columns"));
+    if (n && !dev_keys) return set_err(c, PHJ_ERR_INVALID, "null device key column");
+    if (reinterpret_cast<uintptr_t>(dev_keys) % 8 || reinterpret_cast<uintptr_t>(dev_payloads) % 8)
+        return set_err(c, PHJ_ERR_INVALID, "columns must be 8-byte aligned");
+    bind_columns_state(c, side, dev_keys, dev_payloads, n, false);
+    return PHJ_OK;
+}
+
+int phj_relation_to_columns(phj_ctx* c, int side, int with_payloads) {
+    PHJ_TRY(columns_guard(c, side, "phj_relation_to_columns"));
+    SideState& S = c->side[side];
+    if (S.columns) {   // already columns: only the payload column may go, and with it a packed copy that holds it
+        if (!with_payloads && S.cpays) {
+            S.cpays = nullptr;
+            S.packed = false;
+            S.rel = nullptr;
+            S.partitioned = false;
+        }
+        return PHJ_OK;
+    }
+    if (!S.rel && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    const uint64_t n = S.n;
+    PHJ_TRY(ensure(c, S.ck, n * 8));
+    if (with_payloads) PHJ_TRY(ensure(c, S.cp, n * 8));
+    if (n) {
+        const uint32_t g = static_cast<uint32_t>(std::min<uint64_t>((n + kBlock - 1) / kBlock, 65536));
+        hipLaunchKernelGGL(k_split_columns, dim3(g), dim3(kBlock), 0, c->ks, reinterpret_cast<const longlong2*>(S.rel), n,
+                           static_cast<int64_t*>(S.ck.p), with_payloads ? static_cast<int64_t*>(S.cp.p) : nullptr);
+        PHJ_LAUNCHED(c, "k_split_columns");
+        PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    }
+    bind_columns_state(c, side, static_cast<const int64_t*>(S.ck.p), with_payloads ? static_cast<const int64_t*>(S.cp.p) : nullptr, n, true);
+    return PHJ_OK;
+}
+
+int phj_relation_columns(phj_ctx* c, int side, const int64_t** keys, const int64_t** payloads, uint64_t* n) {
+    PHJ_TRY(columns_guard(c, side, "phj_relation_columns"));
+    const SideState& S = c->side[side];
+    if (keys) *keys = S.columns ? S.ckeys : nullptr;
+    if (payloads) *payloads = S.columns ? S.cpays : nullptr;
+    if (n) *n = S.n;
+    return PHJ_OK;
+}
+
+int phj_relation_info_get(phj_ctx* c, int side, phj_relation_info* out) {
+    PHJ_TRY(columns_guard(c, side, "phj_relation_info_get"));
+    if (!out) return set_err(c, PHJ_ERR_INVALID, "null destination");
+    const SideState& S = c->side[side];
+    out->n = S.n;
+    out->layout = S.columns ? PHJ_LAYOUT_COLUMNS : PHJ_LAYOUT_TUPLES;
+    out->has_payloads = !S.columns || S.cpays ? 1u : 0u;
+    out->packed = S.columns && S.packed ? 1u : 0u;
+    out->owned = S.columns ? (S.cols_owned ? 1u : 0u) : (S.rel && S.rel == S.owned.p ? 1u : 0u);
     return PHJ_OK;
 }
 
@@ -3274,7 +3492,12 @@ int phj_relation_count_in_range(phj_ctx* c, int side, int64_t lo, int64_t hi, ui
     SideState& S = c->side[side];
     PHJ_TRY(ensure(c, c->count, 8));
     PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
-    if (S.n) {
+    if (S.n && S.columns) {   // over the key column itself
+        const uint32_t g = static_cast<uint32_t>(std::min<uint64_t>((S.n + kBlock - 1) / kBlock, 8192));
+        hipLaunchKernelGGL(k_count_range_col, dim3(g), dim3(kBlock), 0, c->ks, S.ckeys, S.n, lo, hi,
+                           static_cast<unsigned long long*>(c->count.p));
+        PHJ_LAUNCHED(c, "k_count_range_col");
+    } else if (S.n) {
         const uint32_t g = static_cast<uint32_t>(std::min<uint64_t>((S.n + kBlock - 1) / kBlock, 8192));
         hipLaunchKernelGGL(k_count_range, dim3(g), dim3(kBlock), 0, c->ks, reinterpret_cast<const longlong2*>(S.rel),
                            S.n, lo, hi, static_cast<unsigned long long*>(c->count.p));
@@ -3296,6 +3519,7 @@ int phj_partition(phj_ctx* c, int side, const phj_join_params* p, phj_partitione
     c->defer_timers = false;
     c->lean_timers = false;
     if (c->timers.size() > kMaxTimerRecs) reset_timers(c);
+    PHJ_TRY(need_tuples(c, side, false, "phj_partition"));   // (bound as columns: the payloads of a key column alone are 0)
     PHJ_TRY(partition_side(c, side, pl));
     if (out) *out = c->side[side].view;
     return PHJ_OK;
@@ -3372,7 +3596,10 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     c->count_pinned = false;
     c->hot_ran = false;
     if (!c->defer_timers || c->timers.size() > kMaxTimerRecs) reset_timers(c);
-    if (p->algo == PHJ_ALGO_NO_PARTITIONING) return join_nopart(c, p, r);
+    if (p->algo == PHJ_ALGO_NO_PARTITIONING) {
+        PHJ_TRY(need_tuples_both(c, false, "phj_join"));   // (sides bound as columns)
+        return join_nopart(c, p, r);
+    }
     if (p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
     Plan pl;
     PHJ_TRY(make_plan(c, p, pl));
@@ -3382,6 +3609,11 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     hipEvent_t t0, t1, tr, b0, b1, p1;
     Plan cpl;
     if (use_cluster(c, pl, S.n, R.n, cpl)) {
+        // a side bound as columns: its code pass reads the key column where it
+        // has the column form (cols_native), else the side is packed first
+        const bool s_cols = cols_native(c, S, cpl, false), r_cols = cols_native(c, R, cpl, true);
+        if (!r_cols) PHJ_TRY(need_tuples(c, PHJ_SIDE_BUILD, false, "phj_join"));
+        if (!s_cols) PHJ_TRY(need_tuples(c, PHJ_SIDE_PROBE, false, "phj_join"));
         // the LDS join (phj_cluster.h): S's pass 1 into clusters (codes) on
         // the main stream; R's pass 1 and the big clusters' HBM tables on the
         // aux stream beside it; then the probe builds each cluster's table in
@@ -3531,10 +3763,12 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         r->total_ms = elapsed(c, t0, p1);
         r->num_partitions = requested;
         // R: 16 read + 8 written (pass 1), 8 read (probe); S: 16 read + 8 written, 8 read
-        r->algorithmic_bytes = R.n * (24 + 8) + S.n * (24 + 8);
+        // (a key column: 8 read in pass 1)
+        r->algorithmic_bytes = R.n * (24 + 8) + S.n * (24 + 8) - (r_cols ? R.n * 8 : 0) - (s_cols ? S.n * 8 : 0);
         hot_scope.ok = true;
         return fill_timers(c, r);
     }
+    PHJ_TRY(need_tuples_both(c, false, "phj_join"));   // (sides bound as columns: no column form on these paths)
     refine_plan(c, pl, R.n);
     if (use_p2probe(c, pl, S.n, R.n)) {
         // S: pass 1 only (its pass 2 runs inside the probe); R: pass 1 as codes
@@ -3629,6 +3863,7 @@ int phj_prepare(phj_ctx* c, const phj_join_params* p) {
     c->dry = true;
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) {
         phj_join_result r{};
+        PHJ_TRY(need_tuples_both(c, false, "phj_prepare"));
         return join_nopart(c, p, &r);
     }
     if (p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
@@ -3636,6 +3871,9 @@ int phj_prepare(phj_ctx* c, const phj_join_params* p) {
     PHJ_TRY(make_plan(c, p, pl));
     if (use_cluster(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n, cpl)) {
         const uint64_t nR = c->side[PHJ_SIDE_BUILD].n;
+        // (sides bound as columns: the tuple copy of a side phj_join would pack)
+        if (!cols_native(c, c->side[PHJ_SIDE_BUILD], cpl, true)) PHJ_TRY(need_tuples(c, PHJ_SIDE_BUILD, false, "phj_prepare"));
+        if (!cols_native(c, c->side[PHJ_SIDE_PROBE], cpl, false)) PHJ_TRY(need_tuples(c, PHJ_SIDE_PROBE, false, "phj_prepare"));
         if (PHJ_PREAGG) PHJ_TRY(ensure(c, c->hot, hot_state_bytes(cpl.nb1)));
         PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, cpl, true));
         PHJ_TRY(ensure(c, c->r_codes, std::max<uint64_t>(1, nR) * 8));
@@ -3645,6 +3883,7 @@ int phj_prepare(phj_ctx* c, const phj_join_params* p) {
         PHJ_HIP(c, hipStreamSynchronize(c->stream));
         return PHJ_OK;
     }
+    PHJ_TRY(need_tuples_both(c, false, "phj_prepare"));
     refine_plan(c, pl, c->side[PHJ_SIDE_BUILD].n);
     if (use_p2probe(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n)) {
         const uint64_t nR = c->side[PHJ_SIDE_BUILD].n;
@@ -3723,6 +3962,7 @@ int phj_join_materialize(phj_ctx* c, const phj_join_params* p, phj_join_result* 
     c->lean_timers = false;
     reset_timers(c);
     c->mat_n = 0;
+    PHJ_TRY(need_tuples_both(c, true, "phj_join_materialize"));   // (sides bound as columns)
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) {
         SideState& S = c->side[PHJ_SIDE_PROBE];
         if (S.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
@@ -3828,6 +4068,7 @@ int phj_probe_pass1(phj_ctx* c, const phj_join_params* p, int64_t* keys, uint64_
     c->lean_timers = false;
     reset_timers(c);
     c->ks = c->stream;
+    if (!cols_native(c, S, pl, false)) PHJ_TRY(need_tuples(c, PHJ_SIDE_PROBE, false, "phj_probe_pass1"));   // (bound as columns)
     PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl, true));
     const uint32_t nt = S.nt2;
     PHJ_TRY(ensure(c, c->prep, (static_cast<size_t>(nt) + 1) * 4));

@@ -72,7 +72,7 @@ static_assert(kHotTilesPerWg * kHotTile <= 65535, "k_hot_sample: the 16-bit halv
 static_assert(kHotCounters % (4 * kHotBlock) == 0, "k_hot_select: whole 16-B loads of counters per thread");
 
 struct HotArgs {
-    const int64_t* rel;     // S: {id, payload} pairs
+    const int64_t* rel;     // S: {id, payload} pairs (k_hot_sample COLS: its key column)
     uint32_t n, ntiles;     // tuples, kHotTile-tuple tiles
     uint32_t nsamp;         // sample tiles (<= ntiles)
     uint32_t thr;           // sample count of a hot code
@@ -119,7 +119,8 @@ __global__ __launch_bounds__(kHotBlock) void k_hot_clear(HotArgs a) {
 // word, the non-zero counters are added to the global ones (the same number
 // of atomic instructions however many tiles were counted) and the workgroup
 // votes. No workgroup waits for another: the selection is the next launch.
-template <int HK>
+// COLS: a.rel is the probe side's key column (a relation bound as columns).
+template <int HK, bool COLS = false>
 __global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hot_lds[];   // [kHotCounters / 2]
     __shared__ uint32_t sum;
@@ -141,7 +142,8 @@ __global__ __launch_bounds__(kHotBlock) void k_hot_sample(HotArgs a) {
         const uint32_t si = s0 + k / I;
         const uint32_t ix = hot_tile_of(a, si < s1 ? si : s0) * kHotTile + (k % I) * kHotBlock + tid;
         const bool ok = si < s1 && ix < a.n;
-        key[k] = rel[ok ? ix : 0].x;
+        if constexpr (COLS) key[k] = a.rel[ok ? ix : 0];
+        else key[k] = rel[ok ? ix : 0].x;
         have |= (ok ? 1u : 0u) << k;
     }
 #pragma unroll

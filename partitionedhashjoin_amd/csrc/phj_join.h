@@ -1236,6 +1236,48 @@ __global__ __launch_bounds__(kBlock) void k_count_range(const longlong2* rel, ui
     }
 }
 
+// Columnar relations (phj_relation_bind_columns ...). k_pack_columns: the
+// tuple copy {keys[i], pays[i]} the calls without a column form run on (pays
+// null, a key column alone: payload 0). k_split_columns: a tuple relation into
+// columns (pays null: the keys only). k_count_range_col: k_count_range over a
+// key column. Every index is below n: nothing beside the columns is touched.
+__global__ __launch_bounds__(kBlock) void k_pack_columns(const int64_t* keys, const int64_t* pays, uint64_t n,
+                                                         longlong2* out) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride)
+        out[i] = make_longlong2(keys[i], pays ? pays[i] : 0);
+}
+
+__global__ __launch_bounds__(kBlock) void k_split_columns(const longlong2* rel, uint64_t n, int64_t* keys,
+                                                          int64_t* pays) {
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+        const longlong2 t = rel[i];
+        keys[i] = t.x;
+        if (pays) pays[i] = t.y;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_count_range_col(const int64_t* keys, uint64_t n, int64_t lo, int64_t hi,
+                                                            unsigned long long* count) {
+    __shared__ uint32_t red[kWaves];
+    uint32_t c = 0;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
+        const int64_t k = keys[i];
+        c += (k >= lo && k <= hi) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < kWaves; w++) t += red[w];
+        if (t) atomicAdd(count, t);
+    }
+}
+
 template <int HK>
 __global__ __launch_bounds__(kBlock) void k_hash_keys(const int64_t* keys, uint64_t n, uint64_t seed,
                                                       uint64_t* out) {

@@ -1150,7 +1150,19 @@ __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int h
 // holds to the count). A table with no entries, or covering less than
 // hot_min_mass sampled keys, skips the lookups (workgroup-uniform, and the
 // same test as the LDS join's: they read the same words).
-template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0>
+// COLS (a relation bound as columns, phj_relation_bind_columns): a.in_keys is
+// the key column, not the tuples. 1: 8 B per lane and load (a wave's load
+// covers 512 contiguous bytes); 2: 16 B, two neighbouring keys per lane, half
+// the load instructions, items 2p and 2p + 1 of a lane then being neighbours
+// (pipe_elem). 0: tuples, the code as before the column forms.
+typedef long long key_pair __attribute__((ext_vector_type(2), aligned(8)));   // 16 B loaded from an 8-B aligned column
+// element of the tile that is item i of a lane
+template <int COLS>
+__device__ __forceinline__ uint32_t pipe_elem(uint32_t wbase, uint32_t lane, int i) {
+    if constexpr (COLS == 2) return wbase + static_cast<uint32_t>(i >> 1) * 128 + lane * 2 + static_cast<uint32_t>(i & 1);
+    else return wbase + i * 64 + lane;
+}
+template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0, int COLS = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : BLOCK / 256)))
 void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     constexpr int NW = BLOCK / 64;
@@ -1233,15 +1245,39 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     // so no register moves): tile t's keys were requested KPF tiles earlier
     int64_t key[KPF][ITEMS];
     const longlong2* rel = reinterpret_cast<const longlong2*>(a.in_keys);
+    // item i of a lane is element pipe_elem(i) of the tile. Tuples and the
+    // 8-B column form: a wave's load covers 64 consecutive elements. COLS 2:
+    // a lane's 16-B load brings two neighbouring keys, items 2p and 2p + 1.
+    static_assert(COLS == 0 || COLS == 1 || (COLS == 2 && ITEMS % 2 == 0), "COLS 2: whole pairs per lane");
     auto load = [&](int64_t* k, uint32_t t) {
         const uint32_t lo = t * T;
+        if constexpr (COLS == 2) {
+            // the pair clamped to the column's last two keys (host: n >= 2):
+            // only the last key of an odd column then arrives in the pair's
+            // second half (hash_all's tail); 8-B aligned, so any key column serves
 #pragma unroll
-        for (int i = 0; i < ITEMS; i++) {
-            const uint32_t ix = min(lo + wbase + i * 64 + lane, a.n - 1);
-            if (a.nt_load) k[i] = __builtin_nontemporal_load(&rel[ix].x);
-            else k[i] = rel[ix].x;
+            for (int p = 0; p < ITEMS / 2; p++) {
+                const uint32_t ix = min(lo + pipe_elem<COLS>(wbase, lane, 2 * p), a.n - 2);
+                const key_pair* src = reinterpret_cast<const key_pair*>(a.in_keys + ix);
+                const key_pair v = a.nt_load ? __builtin_nontemporal_load(src) : *src;
+                k[2 * p] = v.x;
+                k[2 * p + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < ITEMS; i++) {
+                const uint32_t ix = min(lo + pipe_elem<COLS>(wbase, lane, i), a.n - 1);
+                if constexpr (COLS == 1) {
+                    if (a.nt_load) k[i] = __builtin_nontemporal_load(&a.in_keys[ix]);
+                    else k[i] = a.in_keys[ix];
+                } else {
+                    if (a.nt_load) k[i] = __builtin_nontemporal_load(&rel[ix].x);
+                    else k[i] = rel[ix].x;
+                }
+            }
         }
     };
+    (void)rel;
 
     for (uint32_t i = tid; i < 2 * nb; i += BLOCK) wcnt[i] = 0;
 #pragma unroll
@@ -1307,9 +1343,16 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             auto hash_all = [&](auto form, auto full) {
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
-                    const uint64_t h = hash64<HK>(static_cast<uint64_t>(key[kb][i]), a.f.seed);
+                    uint64_t h;
+                    if constexpr (COLS == 2 && !decltype(full)::value) {
+                        // (load's clamp: an odd column's last key is the second of its pair)
+                        const bool tail = (i & 1) == 0 && pipe_elem<COLS>(wbase, lane, i) + 1 == cnt;
+                        h = hash64<HK>(static_cast<uint64_t>(tail ? key[kb][i | 1] : key[kb][i]), a.f.seed);
+                    } else {
+                        h = hash64<HK>(static_cast<uint64_t>(key[kb][i]), a.f.seed);
+                    }
                     code[i] = static_cast<int64_t>(h);
-                    dig[i] = decltype(full)::value || wbase + i * 64 + lane < cnt ? code_digit(h, form) : 0u;
+                    dig[i] = decltype(full)::value || pipe_elem<COLS>(wbase, lane, i) < cnt ? code_digit(h, form) : 0u;
                 }
             };
             if (dform == 2 && cnt == static_cast<uint32_t>(T)) hash_all(F2{}, std::true_type{});
@@ -1324,7 +1367,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             if constexpr (HOT != 0) {
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
-                    keep |= (wbase + i * 64 + lane < cnt ? 1u : 0u) << i;
+                    keep |= (pipe_elem<COLS>(wbase, lane, i) < cnt ? 1u : 0u) << i;
                     hew[i] = 0;
                 }
                 if (hot) {
@@ -1380,7 +1423,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
 #endif
             } else {
 #pragma unroll
-                for (int i = 0; i < ITEMS; i++) rank[i] = atomicAdd(&crow[dig[i]], wbase + i * 64 + lane < cnt ? 1u : 0u);
+                for (int i = 0; i < ITEMS; i++) rank[i] = atomicAdd(&crow[dig[i]], pipe_elem<COLS>(wbase, lane, i) < cnt ? 1u : 0u);
             }
         }
         ptick(0);
@@ -1437,7 +1480,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             for (int i = 0; i < ITEMS; i++) base[i] = crow[dig[i]];
 #pragma unroll
             for (int i = 0; i < ITEMS; i++)
-                if (HOT == 1 ? ((keep >> i) & 1u) != 0 : wbase + i * 64 + lane < cnt) sbuf[par * T + base[i] + rank[i]] = code[i];
+                if (HOT == 1 ? ((keep >> i) & 1u) != 0 : pipe_elem<COLS>(wbase, lane, i) < cnt) sbuf[par * T + base[i] + rank[i]] = code[i];
         }
         const uint32_t pp = par ^ 1u;   // the previous tile's buffers
         // the next tile's counter row: the previous tile's, no longer read

@@ -75,6 +75,7 @@ struct GpuConfiguration {
     uint32_t RowClasses = 0;         // --join-kind: Run() returns that kind's rows (phj_join_rows; PHJ_ROWS_* set, 0 = off)
     int64_t NullPayload = INT64_MIN; // ... the payload standing for the missing side of an outer / anti row
     int Aggregate = 0;               // --aggregate totals | groups: 1 / 2, Run() reports the join's aggregates (phj_join_aggregate; 0 = off)
+    bool Columns = false;            // --layout columns: both relations are split into key / payload columns on the device before the join (phj_relation_to_columns)
     std::vector<int> Devices;       // --gpus N / --devices a,b,..: the context's devices (empty: {Device})
     uint32_t ContextFlags = 0;       // --exchange rccl|local: PHJ_CTX_EXCHANGE / PHJ_CTX_LOCAL
 };

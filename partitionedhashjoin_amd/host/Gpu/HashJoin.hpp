@@ -24,6 +24,9 @@
 // (phj_join_aggregate: `pairs`, `probe_matched`, `sum_a`, `sum_b`, `sum_ab`
 // added to the results; for groups also `groups` and `groups_checksum` over
 // the group rows copied back); the returned table is empty, matches = pairs.
+// GpuConfiguration::Columns binds both relations as key / payload columns
+// (phj_relation_to_columns) before whatever was asked for runs; the results'
+// `layout` says which binding ran.
 // C ABI errors surface as std::runtime_error / std::invalid_argument, which the
 // CLI catches and turns into exit(1) (src/main.cpp:277-281).
 #pragma once
@@ -140,12 +143,21 @@ inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, con
     return out;
 }
 
-inline void add_device_results(Common::IHashJoinTimer& timer, const phj_join_result& r, int gpus) {
+// --layout columns: both resident relations become key / payload columns on
+// the device before the workspace is sized and the join runs
+inline void apply_layout(Device& dev, const Common::GpuConfiguration& gpu) {
+    if (!gpu.Columns) return;
+    dev.Check(phj_relation_to_columns(dev.Get(), PHJ_SIDE_BUILD, 1));
+    dev.Check(phj_relation_to_columns(dev.Get(), PHJ_SIDE_PROBE, 1));
+}
+
+inline void add_device_results(Common::IHashJoinTimer& timer, const phj_join_result& r, int gpus, bool columns = false) {
     timer.AddResult("matches", std::to_string(r.matches));
     timer.AddResult("gpus", std::to_string(gpus));
     timer.AddResult("exchange_us", std::to_string(static_cast<int64_t>(std::llround(r.exchange_ms * 1e3))));
     timer.AddResult("device_total_us", std::to_string(static_cast<int64_t>(std::llround(r.total_ms * 1e3))));
     timer.AddResult("algorithmic_bytes", std::to_string(r.algorithmic_bytes));
+    timer.AddResult("layout", columns ? "columns" : "tuples");
 }
 
 }  // namespace internal
@@ -198,13 +210,14 @@ class HashJoiner {
         std::memset(&r, 0, sizeof(r));
         // workspace allocation stays outside the timed phases, as the reference's
         // partitioned-table allocation does (RadixCluster/HashJoin.hpp:195-198)
+        internal::apply_layout(*m_device, m_gpu);
         m_device->Check(phj_prepare(m_device->Get(), &p));
         auto joined = internal::join(*m_device, p, r, m_gpu, *timer);
         // partition: wall of both partition pipelines; build / probe: device phases
         timer->SetPartitionPhaseDuration(internal::ms_to_ns(r.partition_ms));
         timer->SetBuildPhaseDuration(internal::ms_to_ns(r.build_ms));
         timer->SetProbePhaseDuration(internal::ms_to_ns(r.probe_ms));
-        internal::add_device_results(*timer, r, m_device->NumberOfGpus());
+        internal::add_device_results(*timer, r, m_device->NumberOfGpus(), m_gpu.Columns);
         timer->AddResult("partitions", std::to_string(r.num_partitions));
         m_joined = r.matches;
         m_last = r;
@@ -265,13 +278,14 @@ class HashJoiner {
         std::memset(&r, 0, sizeof(r));
         // workspace allocation stays outside the timed phases, as the reference's
         // partitioned-table allocation does (RadixCluster/HashJoin.hpp:195-198)
+        internal::apply_layout(*m_device, m_gpu);
         m_device->Check(phj_prepare(m_device->Get(), &p));
         auto joined = internal::join(*m_device, p, r, m_gpu, *timer);
         timer->SetBuildPhaseDuration(internal::ms_to_ns(r.build_ms));
         // the reference's probe figure runs from the build start (Results.hpp:202)
         timer->SetProbePhaseDuration(internal::ms_to_ns(r.build_ms + r.probe_ms));
         timer->SetPartitionPhaseDuration(std::chrono::nanoseconds(0));
-        internal::add_device_results(*timer, r, m_device->NumberOfGpus());
+        internal::add_device_results(*timer, r, m_device->NumberOfGpus(), m_gpu.Columns);
         timer->AddResult("probe_only_us", std::to_string(static_cast<int64_t>(std::llround(r.probe_ms * 1e3))));
         m_joined = r.matches;
         m_last = r;

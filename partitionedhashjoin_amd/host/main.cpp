@@ -18,6 +18,7 @@
 //   --exchange rccl|local  force the multi-GPU path (RCCL world of one / device copies)
 //   --join-kind K         inner|probe-outer|build-outer|full-outer|probe-anti|build-anti: return that kind's rows
 //   --aggregate A         totals|groups: report the join's aggregates instead of rows
+//   --layout L            tuples|columns: bind the relations as {id, payload} tuples or as key / payload columns
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -74,6 +75,10 @@ const char* kHelp =
     "                                      pairs, probe_matched, sum_a, sum_b, sum_ab; groups: also one row per\n"
     "                                      build tuple {partners, sum of their payloads}, reported as a count\n"
     "                                      and a checksum. One device only, and not together with returned rows.\n"
+    "  --layout arg (=tuples)              tuples | columns: how the relations are bound. columns: both are split\n"
+    "                                      into a key and a payload column on the device (phj_relation_to_columns)\n"
+    "                                      before the join; the counting join then reads the key columns only.\n"
+    "                                      One device only.\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
@@ -108,7 +113,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
     static const std::set<std::string> known = {"help", "primary", "secondary", "skew", "log", "join", "format",
                                                 "unit", "output", "filename", "partitions", "device", "gpus", "devices", "exchange", "hash",
                                                 "radix-bits", "seed", "hash-seed", "generate", "table-ratio",
-                                                "materialize", "join-kind", "aggregate"};
+                                                "materialize", "join-kind", "aggregate", "layout"};
     Common::Configuration c{};
     c.OutputFormatConfig.TimeUnit = "ms";
     c.OutputConfig.File.Name = "hashjoin.txt";
@@ -179,6 +184,11 @@ Common::Configuration parseArguments(int argc, char** argv) {
             else if (vm["aggregate"] == "groups") c.GpuConfig.Aggregate = 2;
             else throw std::invalid_argument("the argument ('" + vm["aggregate"] + "') for option '--aggregate' is invalid");
         }
+        if (vm.count("layout")) {
+            if (vm["layout"] == "columns") c.GpuConfig.Columns = true;
+            else if (vm["layout"] != "tuples")
+                throw std::invalid_argument("the argument ('" + vm["layout"] + "') for option '--layout' is invalid");
+        }
         c.GpuConfig.Hash = PHJ_HASH_XXH3;
         if (vm.count("hash")) {
             if (vm["hash"] == "xxh3" || vm["hash"] == "xxhash") c.GpuConfig.Hash = PHJ_HASH_XXH3;
@@ -241,6 +251,8 @@ Common::Configuration parseArguments(int argc, char** argv) {
             throw std::invalid_argument("--aggregate returns no rows: not together with --materialize on / all or --join-kind");
         if (c.GpuConfig.Aggregate && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--aggregate runs on one device");
+        if (c.GpuConfig.Columns && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
+            throw std::invalid_argument("--layout columns runs on one device");
         // validateParsedConfiguration (src/Arguments.hpp:7-18)
         c.OutputConfig.Validate();
         c.OutputFormatConfig.Validate();

@@ -25,6 +25,11 @@ c = phj.Context(0)
 c.generate_sequential(0, args.primary, int(os.environ.get("PMC_BUILD_START", "1")))
 c.generate_zipf(1, args.secondary, alpha, 1, args.primary, 20240601)
 c.count_in_range(1, 1, args.primary)
+# PMC_LAYOUT=columns: both relations as key columns alone (the LDS join's code
+# passes then read 8 B per tuple: their FETCH_SIZE against the tuple form's)
+if os.environ.get("PMC_LAYOUT") == "columns":
+    c.to_columns(0, payloads=False)
+    c.to_columns(1, payloads=False)
 for _ in range(args.steps):
     r = c.join(params)
 print("matches", r.matches)
