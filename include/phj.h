@@ -269,6 +269,8 @@ int phj_relation_count_in_range(phj_ctx *ctx, int side, int64_t lo, int64_t hi, 
  *  - phj_join's counting LDS join (PHJ_PATH_LDS_JOIN) in its default schedule
  *    reads the key column itself: 8 B per tuple in pass 1 instead of the 16-B
  *    tuple, no copy made, the payload column never touched.
+ *  - phj_join_indices reads the key column of either side on every path and
+ *    packs nothing (see "row-number joins" below).
  *  - Every other call (phj_join on its other paths, phj_join_materialize,
  *    phj_join_inner[_count], phj_join_rows[_count], phj_join_aggregate,
  *    phj_partition, phj_probe_pass1 off the native pass) packs the side once
@@ -429,6 +431,67 @@ int phj_join_rows(phj_ctx *ctx, const phj_join_params *p, uint32_t classes, int6
 const phj_joined *phj_joined_rows(phj_ctx *ctx, uint64_t *n);
 /* Copy the first n rows of the last phj_join_materialize / phj_join_inner / phj_join_rows to host memory. */
 int phj_joined_download(phj_ctx *ctx, phj_joined *host, uint64_t n);
+
+/* ---- row-number joins: index pairs from key columns, and a gather ----
+ * Replaces nothing in the reference, whose relations have one payload. A
+ * caller with many columns per relation wants the gather map of a join: which
+ * build row goes with which probe row. phj_join_indices is phj_join_rows
+ * returning that map as two int64 index columns, and it reads nothing but
+ * keys; the caller then gathers any number of columns with the map (torch's
+ * index_select takes the columns as they are, or phj_gather_column).
+ *  - One row (build_rows[k], probe_rows[k]) per row that phj_join_rows would
+ *    write for the same classes. Row numbers are positions in the relation as
+ *    bound, 0-based.
+ *  - Row order is phj_join_rows' contract: the probe part first, grouped by
+ *    probe tuple in the probe side's storage order; a probe tuple without a
+ *    partner sits at its place with build_rows == PHJ_NO_ROW; the build-only
+ *    rows follow in unspecified order with probe_rows == PHJ_NO_ROW. On
+ *    NoPartitioning storage order is input order, so probe_rows of the probe
+ *    part is non-decreasing.
+ *  - Every binding works and only keys are read: of a side bound as columns
+ *    the key column (the payload column is never touched, and a key column
+ *    alone is enough), of a side bound as tuples the ids (8 B at stride 16).
+ *    Nothing is packed: phj_relation_info.packed stays as it was and no
+ *    `*.pack` timer appears. Pass 1 (and the NoPartitioning probe) take each
+ *    tuple's position as the payload they move.
+ *  - phj_join_rows' rules carry over: PHJ_ALGO_RADIX with its precondition and
+ *    PHJ_ALGO_NO_PARTITIONING; single-device contexts only (PHJ_ERR_STATE,
+ *    "single-device contexts only"); classes == 0 or a bit above 0x4 gives
+ *    PHJ_ERR_INVALID; with 2^32 rows or more PHJ_ERR_RANGE before anything is
+ *    written or grown, the counts still filled and 0 index rows reported; an
+ *    empty side is not an error (the other side's tuples are "only", with
+ *    indices 0 .. n-1, no join runs; both sides empty: 0 rows).
+ *  - One result at a time, and the two kinds may share memory: an index join
+ *    replaces the rows of an earlier materialised join (phj_joined_rows then
+ *    reports 0), and phj_join_materialize, phj_join_inner and phj_join_rows
+ *    replace the index columns (phj_joined_indices then reports 0).
+ *    phj_join_rows_count, phj_join_inner_count and phj_join_aggregate disturb
+ *    neither.
+ *  - Timers are phj_join_rows' (`rows.count`, `rows.emit`, `rows.build_only`)
+ *    beside the partition / np.build timers. Bytes: 16 per row written where
+ *    phj_join_rows writes 24; a side whose pass 1 reads a key column is
+ *    accounted 8 B read per tuple where the tuple form reads 16 (`X.p1.hist`
+ *    n * 8, `X.p1.scatter` n * 24; the chunked pass n * 24);
+ *    algorithmic_bytes follows (DESIGN.md §3 "Row-number joins").
+ * Synchronous. */
+#define PHJ_NO_ROW (-1)   /* the missing side's row number in an outer / anti join */
+int phj_join_indices(phj_ctx *ctx, const phj_join_params *p, uint32_t classes,
+                     phj_join_result *r, phj_row_counts *n);
+/* Device pointers of the last index join's columns (ctx-owned, valid until the
+ * next materialised or index join; NULL when there are no rows) and the row count. */
+int phj_joined_indices(phj_ctx *ctx, const int64_t **build_rows, const int64_t **probe_rows, uint64_t *n);
+/* Copy the first n entries of either column (NULL: skip it) to host OR device memory. */
+int phj_joined_indices_download(phj_ctx *ctx, int64_t *build_rows, int64_t *probe_rows, uint64_t n);
+/* out[i] = src[idx[i]] for i in [0, n); idx[i] == PHJ_NO_ROW gives *null_value,
+ * or leaves out[i] as it is when null_value is NULL (so two gathers compose a
+ * coalesce). All pointers but null_value are device addresses, 8-byte aligned.
+ *  - Synchronous, on the context's stream; n == 0 is PHJ_OK.
+ *  - An index outside [0, src_n) other than PHJ_NO_ROW is never dereferenced:
+ *    its out[i] gets the null treatment and the call returns PHJ_ERR_RANGE
+ *    after the kernel, the message saying how many there were.
+ *  - Single-device contexts only: a group or rank context returns PHJ_ERR_STATE. */
+int phj_gather_column(phj_ctx *ctx, const int64_t *src, uint64_t src_n, const int64_t *idx, uint64_t n,
+                      const int64_t *null_value, int64_t *out);
 
 /* ---- aggregates over the join, without its rows ----
  * Replaces nothing in the reference, which only counts. What a caller usually

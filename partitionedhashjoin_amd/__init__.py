@@ -18,7 +18,7 @@ from ._capi import (AGG_GROUPS, AGG_MATCHED_ONLY, ALGO_NO_PARTITIONING, ALGO_RAD
                     HASH_MURMUR3, HASH_XXH3, INNER, NULL_PAYLOAD, PATH_CODE_TABLES, PATH_LDS_JOIN,
                     PATH_NO_PARTITIONING, PATH_PARTITIONED, PROBE_ANTI, PROBE_OUTER, ROWS_BUILD_ONLY, ROWS_PAIRS,
                     ROWS_PROBE_ONLY, SIDE_BUILD, SIDE_PROBE, GroupRow, JoinParams, JoinResult, JoinTotals, Partitioned,
-                    PhjError, RowCounts, LAYOUT_TUPLES, LAYOUT_COLUMNS, RelationInfo)
+                    PhjError, RowCounts, LAYOUT_TUPLES, LAYOUT_COLUMNS, RelationInfo, NO_ROW)
 
 __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_JOIN", "PATH_CODE_TABLES",
            "PATH_PARTITIONED", "PATH_NO_PARTITIONING", "count_contribution", "count_verdict", "comm_unique_id", "CTX_EXCHANGE", "CTX_LOCAL", "radix_params", "nopart_params", "JoinParams", "JoinResult",
@@ -26,7 +26,7 @@ __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_J
            "HASH_MURMUR3", "SIDE_BUILD", "SIDE_PROBE", "DEFAULT_SEED", "RowCounts", "ROWS_PAIRS", "ROWS_PROBE_ONLY",
            "ROWS_BUILD_ONLY", "INNER", "PROBE_OUTER", "BUILD_OUTER", "FULL_OUTER", "PROBE_ANTI", "BUILD_ANTI",
            "NULL_PAYLOAD", "JoinTotals", "GroupRow", "AGG_GROUPS", "AGG_MATCHED_ONLY",
-           "RelationInfo", "LAYOUT_TUPLES", "LAYOUT_COLUMNS"]
+           "RelationInfo", "LAYOUT_TUPLES", "LAYOUT_COLUMNS", "NO_ROW"]
 
 DEFAULT_SEED = 0x9E3779B97F4A7C15
 PART_STABLE = 0x1   # include/phj.h PHJ_PART_STABLE
@@ -347,6 +347,49 @@ class Context:
         out = np.zeros((n, 3), dtype=np.int64)
         self._check(self._L.phj_joined_download(self._h, out.ctypes.data_as(C.c_void_p), n))
         return out
+
+    def join_indices(self, params: JoinParams, classes: int):
+        """phj_join_indices: the join kind `classes` as two int64 index columns
+        (build row, probe row; NO_ROW for the missing side), in join_rows' row
+        order. Only keys are read: any binding will do, a key column alone
+        included, and nothing is packed. Returns (JoinResult, RowCounts); read
+        the columns with joined_indices() or hand joined_indices_ptr() to a
+        gather. Raises PhjError (PHJ_ERR_RANGE) at 2^32 rows or more."""
+        r, n = JoinResult(), RowCounts()
+        self._check(self._L.phj_join_indices(self._h, C.byref(params), classes, C.byref(r), C.byref(n)))
+        return r, n
+
+    def joined_indices_ptr(self):
+        """(build_rows device pointer, probe_rows device pointer, n) of the last
+        join_indices: ctx-owned, valid until the next materialised or index
+        join; the pointers are None when there are no rows."""
+        b, p, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        self._check(self._L.phj_joined_indices(self._h, C.byref(b), C.byref(p), C.byref(n)))
+        return b.value, p.value, n.value
+
+    def joined_indices(self, n: int | None = None):
+        """The index columns of the last join_indices as two np.int64 arrays
+        (build_rows, probe_rows)."""
+        n = self.joined_indices_ptr()[2] if n is None else n
+        b, p = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        self._check(self._L.phj_joined_indices_download(self._h, b.ctypes.data_as(C.c_void_p),
+                                                        p.ctypes.data_as(C.c_void_p), n))
+        return b, p
+
+    def joined_indices_to(self, build_ptr: int | None, probe_ptr: int | None, n: int) -> None:
+        """Copy the first n entries of the index columns to device memory at
+        build_ptr / probe_ptr (None: skip that column)."""
+        self._check(self._L.phj_joined_indices_download(self._h, C.c_void_p(build_ptr), C.c_void_p(probe_ptr), n))
+
+    def gather_column(self, src_ptr: int, src_n: int, idx_ptr: int, n: int, null_value: int | None,
+                      out_ptr: int) -> None:
+        """phj_gather_column on device pointers: out[i] = src[idx[i]]; where
+        idx[i] == NO_ROW, out[i] = null_value, or stays as it is when
+        null_value is None. Raises PhjError (PHJ_ERR_RANGE) when other indices
+        lay outside [0, src_n): they are not dereferenced."""
+        nv = None if null_value is None else C.byref(C.c_int64(null_value))
+        self._check(self._L.phj_gather_column(self._h, C.c_void_p(src_ptr), src_n, C.c_void_p(idx_ptr), n, nv,
+                                              C.c_void_p(out_ptr)))
 
     def join_aggregate(self, params: JoinParams, groups: bool = False, matched_only: bool = False):
         """phj_join_aggregate: (JoinResult, JoinTotals) of R join S without its

@@ -44,6 +44,7 @@ EXPORTED = [
     "phj_debug_preagg", "phj_join_aggregate", "phj_group_rows", "phj_group_download",
     "phj_relation_upload_columns", "phj_relation_bind_columns", "phj_relation_to_columns",
     "phj_relation_columns", "phj_relation_info_get",
+    "phj_join_indices", "phj_joined_indices", "phj_joined_indices_download", "phj_gather_column",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
@@ -56,6 +57,7 @@ INNER, PROBE_OUTER, BUILD_OUTER, FULL_OUTER, PROBE_ANTI, BUILD_ANTI = 1, 3, 5, 7
 NULL_PAYLOAD = -2**63   # the default marker for the missing side (INT64_MIN)
 AGG_GROUPS, AGG_MATCHED_ONLY = 0x1, 0x2   # phj_join_aggregate's flags
 LAYOUT_TUPLES, LAYOUT_COLUMNS = 0, 1   # phj_relation_info.layout
+NO_ROW = -1   # PHJ_NO_ROW: the missing side's row number in phj_join_indices' columns
 
 
 class Tuple(C.Structure):
@@ -210,6 +212,11 @@ def load():
                                    C.POINTER(JoinTotals)]),
         "phj_group_rows": (P, [P, C.POINTER(u64)]),
         "phj_group_download": (i, [P, P, u64]),
+        "phj_join_indices": (i, [P, C.POINTER(JoinParams), C.c_uint32, C.POINTER(JoinResult),
+                                 C.POINTER(RowCounts)]),
+        "phj_joined_indices": (i, [P, C.POINTER(P), C.POINTER(P), C.POINTER(u64)]),
+        "phj_joined_indices_download": (i, [P, P, P, u64]),
+        "phj_gather_column": (i, [P, P, u64, P, u64, C.POINTER(i64), P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

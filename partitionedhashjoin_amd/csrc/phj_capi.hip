@@ -57,6 +57,7 @@
 #include "phj_join.h"
 #include "phj_inner.h"
 #include "phj_outer.h"
+#include "phj_index.h"
 #include "phj_agg.h"
 #include "phj_mat.h"
 #include "phj_partition.h"
@@ -209,6 +210,12 @@ struct phj_ctx {
     DevBuf agg_acc, agg_cnt, agg_rows, agg_res;   // phj_join_aggregate: accumulator planes, block offsets, group rows, {5 totals, rows}
     uint64_t agg_n = 0;   // group rows of the last phj_join_aggregate
     uint64_t mat_n = 0;   // fused join: item slots; wave clocks {build, probe} since the last timer reset
+    // phj_join_indices: its two index columns lie in mat_rows, build_rows in
+    // int64 words [0, idx_n), probe_rows in [idx_n, 2 idx_n) (16 B per row
+    // where a materialised join holds 24: one result at a time, so whichever
+    // join ran last zeroes the other's count)
+    uint64_t idx_n = 0;
+    DevBuf gather_bad;    // phj_gather_column: its count of indices out of range
     std::vector<hipEvent_t> evpool;
     size_t evnext = 0;
     std::vector<TimerRec> timers;
@@ -749,9 +756,16 @@ int occupancy(const void* kfn, int block, size_t lds) {
     return occ;
 }
 
-template <int BLOCK, int ITEMS, bool IN_AOS, bool OUT_AOS>
+// ROWS (pass 1 of the row-number joins, phj_index.h): 0 = the payloads are
+// loaded; 1 / 2 = the input is a key column / 16-B tuples whose payloads are
+// ignored, and the payload written is the tuple's row number. Only the passes
+// that move whole tuples have these forms (IN_AOS, never keys_only).
+template <int BLOCK, int ITEMS, bool IN_AOS, bool OUT_AOS, int ROWS = 0>
 int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const std::string& prefix,
                   uint64_t n, uint32_t hist_len) {
+    static_assert(ROWS == 0 || IN_AOS, "row numbers are synthesised by pass 1");
+    if (ROWS != 0 && a.keys_only) return set_err(c, PHJ_ERR_INVALID, "row-number pass 1: no keys-only form");
+    constexpr uint64_t kcol = ROWS == 1 ? 8 : 0;   // bytes per tuple a key column saves the reads
     constexpr int T = BLOCK * ITEMS;
     constexpr int NW = BLOCK / 64;
     const size_t hist_lds = static_cast<size_t>(NW) * a.nbins * 4;
@@ -766,7 +780,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
         else if (!zeroed) PHJ_HIP(c, hipMemsetAsync(a.chunk_cursor, 0, chunk_state_bytes(a.nbins), c->ks));
         c->since_ev++;
         // (a key column, c->p1_cols: 8 B read per tuple, not the 16-B tuple)
-        const uint64_t sbytes = n * (a.keys_only ? 24 : 32) - (c->p1_cols ? n * 8 : 0) + (a.out_dig ? n * (a.dig_wide ? 2 : 1) : 0);
+        const uint64_t sbytes = n * (a.keys_only ? 24 : 32) - (c->p1_cols ? n * 8 : 0) - n * kcol + (a.out_dig ? n * (a.dig_wide ? 2 : 1) : 0);
         PHJ_TRY(timer_begin(c, sname.c_str(), sbytes));
         if constexpr (IN_AOS && OUT_AOS && ITEMS <= 8) {
             // persistent: as many workgroups per shard as fit the chip at once
@@ -827,7 +841,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                     });
             } else
                 kfn = with_hash(hk, [](auto h) {
-                    return reinterpret_cast<const void*>(&k_scatter_chunked<BLOCK, ITEMS, decltype(h)::value, 3>);
+                    return reinterpret_cast<const void*>(&k_scatter_chunked<BLOCK, ITEMS, decltype(h)::value, 3, ROWS>);
                 });
             if (c->p1_cols && !cols_form) return set_err(c, PHJ_ERR_STATE, "key column: this code pass has no column form");
             // workgroups per CU: what the LDS and the kernel's registers allow
@@ -875,7 +889,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
     // algorithmic bytes: the histogram reads the key (a whole 16-B tuple when AoS)
     // or 1-2 B of a digit column; the scatter reads and writes every tuple once
     // (16 + 16 B) plus the digit column it leaves for pass 2
-    const uint64_t hbytes = a.in_dig ? n * (a.dig_wide ? 2 : 1) : n * (IN_AOS ? 16 : 8);
+    const uint64_t hbytes = a.in_dig ? n * (a.dig_wide ? 2 : 1) : n * (IN_AOS ? 16 : 8) - n * kcol;
     PHJ_TRY(timer_begin(c, hname.c_str(), hbytes));
     if (a.in_dig) {
         // wave per tile: 4 tiles per workgroup
@@ -889,16 +903,19 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
             hipLaunchKernelGGL((k_hist_col<T, uint8_t>), dim3(cgrid), dim3(256), clds, c->ks, ac);
     } else
         with_hash(hk, [&](auto h) {
-            hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, IN_AOS, decltype(h)::value>), dim3(grid), dim3(BLOCK), hist_lds, c->ks, a);
+            if constexpr (ROWS == 1)
+                hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, false, decltype(h)::value, true>), dim3(grid), dim3(BLOCK), hist_lds, c->ks, a);
+            else   // (ROWS 2: the tuple form already reads the ids alone)
+                hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, IN_AOS, decltype(h)::value>), dim3(grid), dim3(BLOCK), hist_lds, c->ks, a);
         });
     PHJ_LAUNCHED(c, hname);
     PHJ_TRY(timer_end(c));
     PHJ_TRY(timer_begin(c, cname.c_str(), static_cast<uint64_t>(hist_len) * 12));
     PHJ_TRY(scan_u32(c, a.hist, hist_len, 1, hist_len, c->scan_scratch));
     PHJ_TRY(timer_end(c));
-    PHJ_TRY(timer_begin(c, sname.c_str(), n * 32 + (a.out_dig ? n * (a.dig_wide ? 2 : 1) : 0)));
+    PHJ_TRY(timer_begin(c, sname.c_str(), n * 32 - n * kcol + (a.out_dig ? n * (a.dig_wide ? 2 : 1) : 0)));
     with_hash(hk, [&](auto h) {
-        hipLaunchKernelGGL((k_scatter<BLOCK, ITEMS, IN_AOS, OUT_AOS, decltype(h)::value>), dim3(grid), dim3(BLOCK), sc_lds, c->ks, a);
+        hipLaunchKernelGGL((k_scatter<BLOCK, ITEMS, IN_AOS, OUT_AOS, decltype(h)::value, ROWS>), dim3(grid), dim3(BLOCK), sc_lds, c->ks, a);
     });
     PHJ_LAUNCHED(c, sname);
     PHJ_TRY(timer_end(c));
@@ -920,16 +937,22 @@ TileShape tile_shape(const phj_ctx* c, uint32_t nb) {
 }
 
 // One partition pass over `ntiles` tiles (an upper bound for segmented passes).
+// rows: launch_pass_t's ROWS (pass 1 over the bound relation only).
 int launch_pass(phj_ctx* c, int hk, bool in_aos, bool out_aos, PassArgs a, uint32_t ntiles,
-                const std::string& prefix, uint64_t n, uint32_t hist_len) {
+                const std::string& prefix, uint64_t n, uint32_t hist_len, int rows = 0) {
     if (ntiles == 0) return PHJ_OK;
     uint32_t grid = ntiles;
     grid = (ntiles + 7) & ~7u;
     a.xcd_remap = 1;
     const TileShape sh = tile_shape(c, a.nbins);
     const int io = (in_aos ? 2 : 0) + (out_aos ? 1 : 0);
+    if (rows < 0 || rows > 2 || (rows != 0 && !in_aos)) return set_err(c, PHJ_ERR_INVALID, "unsupported pass layout");
 #define PHJ_PASS_CASES(B, I)                                                        \
-    switch (io) {                                                                   \
+    switch (io + 4 * rows) {   /* (one statement: it follows an unbraced if) */     \
+        case 4 + 2: return launch_pass_t<B, I, true, false, 1>(c, hk, a, grid, prefix, n, hist_len); \
+        case 4 + 3: return launch_pass_t<B, I, true, true, 1>(c, hk, a, grid, prefix, n, hist_len);  \
+        case 8 + 2: return launch_pass_t<B, I, true, false, 2>(c, hk, a, grid, prefix, n, hist_len); \
+        case 8 + 3: return launch_pass_t<B, I, true, true, 2>(c, hk, a, grid, prefix, n, hist_len);  \
         case 0: return launch_pass_t<B, I, false, false>(c, hk, a, grid, prefix, n, hist_len); \
         case 2: return launch_pass_t<B, I, true, false>(c, hk, a, grid, prefix, n, hist_len);  \
         case 3: return launch_pass_t<B, I, true, true>(c, hk, a, grid, prefix, n, hist_len);   \
@@ -992,12 +1015,21 @@ bool cols_native(const phj_ctx* c, const SideState& S, const Plan& pl, bool is_r
     return sh.block == 512 && sh.tile == 4096 && chunked_pass1(c, pl, S.n, true);
 }
 
+// Where pass 1 takes the payload it moves from: the bound payloads, or (the
+// row-number joins, phj_index.h) the tuple's position in the relation as
+// bound. The second form reads nothing but keys: the key column of a columnar
+// binding (even beside a packed copy: half the bytes), or the ids of the
+// tuples, and needs no packed copy.
+enum class PaySrc { Bound, RowNumber };
+
 int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, bool p1_only,
-                    unsigned long long* zero = nullptr, uint32_t max_shards = kShards) {
+                    unsigned long long* zero = nullptr, uint32_t max_shards = kShards, PaySrc pay = PaySrc::Bound) {
     c->scan_scratch = &S.partials;
     if (!S.rel && !S.columns && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    const int rows = pay == PaySrc::Bound ? 0 : S.columns ? 1 : 2;   // launch_pass_t's ROWS
+    if (rows && p1_only) return set_err(c, PHJ_ERR_INVALID, "row numbers: whole tuples are partitioned");
     const bool cols = p1_only && cols_native(c, S, pl, &S == &c->side[PHJ_SIDE_BUILD]);
-    if (!S.rel && !cols && !c->dry && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation bound as columns: no tuple copy was packed for this pass");
+    if (!S.rel && !cols && !rows && !c->dry && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation bound as columns: no tuple copy was packed for this pass");
     const uint64_t n64 = S.n;
     if (n64 >= (1ull << 32) - 2 * 4096) return set_err(c, PHJ_ERR_RANGE, "relation above 2^32 tuples per device");
     const uint32_t n = static_cast<uint32_t>(n64);
@@ -1077,7 +1109,7 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
     }
     // pass 1: AoS relation -> SoA columns A (cols: the key column -> codes)
     PassArgs a{};
-    a.in_keys = cols ? S.ckeys : reinterpret_cast<const int64_t*>(S.rel);
+    a.in_keys = cols || rows == 1 ? S.ckeys : reinterpret_cast<const int64_t*>(S.rel);
     a.out_keys = static_cast<int64_t*>(S.kA.p);
     a.out_pays = static_cast<int64_t*>(S.pA.p);
     a.hist = static_cast<uint32_t*>(S.hist1.p);
@@ -1118,7 +1150,7 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
     }
     uint32_t* tb2 = pl.npass == 2 ? static_cast<uint32_t*>(S.tbase2.p) : nullptr;
     c->p1_cols = cols;
-    const int rc1 = launch_pass(c, pl.hk, true, p1_aos, a, nt1, std::string(tag) + ".p1", n, nt1 * pl.nb1);
+    const int rc1 = launch_pass(c, pl.hk, true, p1_aos, a, nt1, std::string(tag) + ".p1", n, nt1 * pl.nb1, rows);
     c->p1_cols = false;
     PHJ_TRY(rc1);
     if (chunked) {
@@ -1210,8 +1242,9 @@ int partition_state(phj_ctx* c, SideState& S, const char* tag, const Plan& pl, b
 
 // zero: a word the pass-1 bookkeeping clears (the on-chip probe's count),
 // or null
-int partition_side(phj_ctx* c, int s, const Plan& pl, bool p1_only = false, unsigned long long* zero = nullptr) {
-    return partition_state(c, c->side[s], s == PHJ_SIDE_BUILD ? "R" : "S", pl, p1_only, zero);
+int partition_side(phj_ctx* c, int s, const Plan& pl, bool p1_only = false, unsigned long long* zero = nullptr,
+                   PaySrc pay = PaySrc::Bound) {
+    return partition_state(c, c->side[s], s == PHJ_SIDE_BUILD ? "R" : "S", pl, p1_only, zero, kShards, pay);
 }
 
 // Hot-key pre-aggregation (phj_hot.h) for phj_join's counting LDS join in its
@@ -2029,7 +2062,8 @@ int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
 // b * 7 + s must stay below kNoMatch (the materialising probes store it in 32
 // bits). *e0 is recorded before the first kernel. Under phj_prepare (c->dry)
 // only the workspace is sized.
-int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipEvent_t* e0) {
+// pay: what np_pays holds (PaySrc::RowNumber: each build tuple's row number).
+int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipEvent_t* e0, PaySrc pay = PaySrc::Bound) {
     SideState& R = c->side[PHJ_SIDE_BUILD];
     const double ratio = p->table_ratio > 0 ? p->table_ratio : kNPDefaultRatio;
     if (ratio < 1.0) return set_err(c, PHJ_ERR_INVALID, "table_ratio must be >= 1");
@@ -2063,13 +2097,13 @@ int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipE
         pp.radix_bits[1] = static_cast<uint8_t>(g.rbits <= 8 ? 0 : g.rbits / 2);
         pp.radix_bits[0] = static_cast<uint8_t>(g.rbits - pp.radix_bits[1]);
         PHJ_TRY(make_plan(c, &pp, rp));
-        if (c->dry) return partition_side(c, PHJ_SIDE_BUILD, rp);
+        if (c->dry) return partition_side(c, PHJ_SIDE_BUILD, rp, false, nullptr, pay);
     }
     const uint32_t nR = static_cast<uint32_t>(R.n);
     PHJ_TRY(mark(c, e0));
     {
         // the partition is part of the build (its R.* timers show it)
-        PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, rp));
+        PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, rp, false, nullptr, pay));
         const phj_partitioned& v = R.view;
         PHJ_TRY(timer_begin(c, "np.build", static_cast<uint64_t>(nR) * 32 + static_cast<uint64_t>(nb) * 64));
         PHJ_HIP(c, hipMemsetAsync(c->np_ovfn.p, 0, 4, c->ks));
@@ -2245,7 +2279,7 @@ struct FusedJoin {
 
 // Plan, precondition ("<what> needs ..."), both sides partitioned, the
 // workspace sized, the count cleared, the join kernels' arguments and grid.
-int fused_setup(phj_ctx* c, const phj_join_params* p, const char* what, FusedJoin& j) {
+int fused_setup(phj_ctx* c, const phj_join_params* p, const char* what, FusedJoin& j, PaySrc pay = PaySrc::Bound) {
     PHJ_TRY(make_plan(c, p, j.pl));
     SideState& R = c->side[PHJ_SIDE_BUILD];
     SideState& S = c->side[PHJ_SIDE_PROBE];
@@ -2255,8 +2289,8 @@ int fused_setup(phj_ctx* c, const phj_join_params* p, const char* what, FusedJoi
     if (!c->tune.fused || (R.n + P - 1) / P * 3 > static_cast<uint64_t>(kFusedTcap) * 2)
         return set_err(c, PHJ_ERR_INVALID, std::string(what) + " needs the fused LDS join (PHJ_FUSED, PHJ_SUBPART)");
     PHJ_TRY(mark(c, &j.t0));
-    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, j.pl));
-    PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, j.pl));
+    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, j.pl, false, nullptr, pay));
+    PHJ_TRY(partition_side(c, PHJ_SIDE_BUILD, j.pl, false, nullptr, pay));
     PHJ_TRY(mark(c, &j.t1));
     j.nS = S.view.n;
     const size_t nslots = j.nS / kFusedChunk + P + 1;
@@ -2476,7 +2510,7 @@ int join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool em
     c->timer_skipped = false;
     c->count_pinned = false;
     reset_timers(c);
-    if (emit) c->mat_n = 0;
+    if (emit) c->mat_n = c->idx_n = 0;   // (the index columns of phj_join_indices lie in the same buffer)
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
     PHJ_TRY(need_tuples_both(c, emit, what));   // (sides bound as columns)
@@ -2722,16 +2756,17 @@ uint64_t rows_count_bytes(uint64_t inner_count, uint64_t F, uint64_t nS, uint32_
     return inner_count + ((classes & PHJ_ROWS_BUILD_ONLY) ? 2 * F : 0) +
            ((classes & PHJ_ROWS_PROBE_ONLY) ? nS * 8 + nS / 8 : 0);
 }
-uint64_t rows_emit_bytes(uint64_t nS, uint64_t pair_rows, uint64_t probe_only, uint64_t build_bytes) {
-    return nS * 12 + (pair_rows ? build_bytes + nS * (16 + 4) + pair_rows * (8 + 24) : 0) +
-           (probe_only ? nS / 8 + probe_only * (4 + 16 + 24) : 0);
+// row: bytes written per row, 24 (phj_joined) or 16 (the two index columns).
+uint64_t rows_emit_bytes(uint64_t nS, uint64_t pair_rows, uint64_t probe_only, uint64_t build_bytes, uint64_t row = 24) {
+    return nS * 12 + (pair_rows ? build_bytes + nS * (16 + 4) + pair_rows * (8 + row) : 0) +
+           (probe_only ? nS / 8 + probe_only * (4 + 16 + row) : 0);
 }
-uint64_t rows_build_only_bytes(uint64_t F, uint64_t table_bytes, uint64_t build_only, bool write) {
-    return F + table_bytes + (write ? build_only * (16 + 24) : 0);
+uint64_t rows_build_only_bytes(uint64_t F, uint64_t table_bytes, uint64_t build_only, bool write, uint64_t row = 24) {
+    return F + table_bytes + (write ? build_only * (16 + row) : 0);
 }
 
-int rows_range_error(phj_ctx* c, uint64_t rows) {
-    return set_err(c, PHJ_ERR_RANGE, "phj_join_rows: " + std::to_string(rows) +
+int rows_range_error(phj_ctx* c, uint64_t rows, bool index = false) {
+    return set_err(c, PHJ_ERR_RANGE, std::string(index ? "phj_join_indices: " : "phj_join_rows: ") + std::to_string(rows) +
                                          " rows, rows are addressed with 32 bits (limit 2^32 - 1)");
 }
 
@@ -2749,7 +2784,18 @@ struct RowsJob {
     uint64_t count_bytes = 0, build_bytes = 0, table_bytes = 0;
     std::function<int(bool)> count;
     std::function<int(JoinedRow*, uint32_t)> emit;
+    // phj_join_indices: the payloads the join carries are row numbers (sp, rp;
+    // NoPartitioning: s_aos and sk are null and a probe tuple's number is its
+    // position) and the emit pass stores into the two index columns
+    bool index = false;
+    std::function<int(IndexSink, uint32_t)> emit_index;
 };
+
+// The two index columns of n rows in the row buffer (phj_ctx::idx_n).
+IndexSink index_sink(phj_ctx* c, uint64_t n) {
+    int64_t* base = static_cast<int64_t*>(c->mat_rows.p);
+    return IndexSink{base, base + n};
+}
 
 // Everything behind the partitioning / table build: the count pass (with hit
 // marking) and the reductions, the counts read back, then (emit) the 2^32
@@ -2809,31 +2855,40 @@ int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, c
     if (!emit) return PHJ_OK;
     // nothing is written and the row buffer is not grown above the limit
     // (below it no block sum of the offsets can have wrapped either)
-    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows);
+    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows, J.index);
+    const uint64_t row_bytes = J.index ? 2 * sizeof(int64_t) : sizeof(JoinedRow);
     PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
-    PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, n->rows) * sizeof(JoinedRow)));
+    PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, n->rows) * row_bytes));
     auto* rows = static_cast<JoinedRow*>(c->mat_rows.p);
+    const IndexSink isink = index_sink(c, n->rows);
     if (probe_rows > 0) {
-        bytes = rows_emit_bytes(J.nS, pair_rows, n->probe_only, J.build_bytes);
+        bytes = rows_emit_bytes(J.nS, pair_rows, n->probe_only, J.build_bytes, row_bytes);
         r->algorithmic_bytes += bytes;
         PHJ_TRY(timer_begin(c, "rows.emit", bytes));
         PHJ_TRY(inner_offsets(c, J.nS));
-        if (pair_rows > 0) PHJ_TRY(J.emit(rows, static_cast<uint32_t>(probe_rows)));
+        if (pair_rows > 0) PHJ_TRY(J.index ? J.emit_index(isink, static_cast<uint32_t>(probe_rows)) : J.emit(rows, static_cast<uint32_t>(probe_rows)));
         if (n->probe_only > 0) {
             const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((J.nS + kBlock - 1) / kBlock, 8192));
-            hipLaunchKernelGGL(k_rows_fill, dim3(grid), dim3(kBlock), 0, c->ks, only, pairs, J.nS, J.s_aos, J.sk, J.sp,
-                               null_payload, rows, static_cast<uint32_t>(probe_rows));
+            if (J.index)
+                hipLaunchKernelGGL(k_rows_fill<IndexSink>, dim3(grid), dim3(kBlock), 0, c->ks, only, pairs, J.nS, J.s_aos, J.sk, J.sp,
+                                   null_payload, isink, static_cast<uint32_t>(probe_rows));
+            else
+                hipLaunchKernelGGL(k_rows_fill<>, dim3(grid), dim3(kBlock), 0, c->ks, only, pairs, J.nS, J.s_aos, J.sk, J.sp,
+                                   null_payload, rows, static_cast<uint32_t>(probe_rows));
             PHJ_LAUNCHED(c, "k_rows_fill");
         }
         PHJ_TRY(timer_end(c));
     }
     if (n->build_only > 0) {
-        bytes = rows_build_only_bytes(J.nF, J.table_bytes, n->build_only, true);
+        bytes = rows_build_only_bytes(J.nF, J.table_bytes, n->build_only, true, row_bytes);
         r->algorithmic_bytes += bytes;
         PHJ_TRY(timer_begin(c, "rows.build_only", bytes));
         PHJ_TRY(scan_u32(c, bcnt, fblk + 1, 1, fblk + 1));
         const uint32_t row0 = static_cast<uint32_t>(probe_rows), nrows = static_cast<uint32_t>(n->rows);
-        if (np) hipLaunchKernelGGL(k_build_only_write<true>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, rows, row0, nrows);
+        if (J.index) {
+            if (np) hipLaunchKernelGGL((k_build_only_write<true, IndexSink>), dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, isink, row0, nrows);
+            else hipLaunchKernelGGL((k_build_only_write<false, IndexSink>), dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, isink, row0, nrows);
+        } else if (np) hipLaunchKernelGGL(k_build_only_write<true>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, rows, row0, nrows);
         else hipLaunchKernelGGL(k_build_only_write<false>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, rows, row0, nrows);
         PHJ_LAUNCHED(c, "k_build_only_write");
         PHJ_TRY(timer_end(c));
@@ -2843,8 +2898,11 @@ int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, c
     return PHJ_OK;
 }
 
+// index (phj_join_indices): the table's payloads are build row numbers
+// (np_build), S is read for its keys alone (k_np_inner KEYS: its key column, or
+// its tuples' ids), a probe tuple's payload is its position.
 int join_nopart_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, bool emit,
-                     phj_join_result* r, phj_row_counts* n) {
+                     phj_join_result* r, phj_row_counts* n, bool index = false) {
     SideState& R = c->side[PHJ_SIDE_BUILD];
     SideState& S = c->side[PHJ_SIDE_PROBE];
     if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
@@ -2855,24 +2913,49 @@ int join_nopart_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int
     hipEvent_t e0 = nullptr, e1, e2;
     PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));
     PHJ_TRY(ensure(c, c->count, 32));
-    PHJ_TRY(np_build(c, p, true, g, &e0));
+    PHJ_TRY(np_build(c, p, true, g, &e0, index ? PaySrc::RowNumber : PaySrc::Bound));
     PHJ_TRY(mark(c, &e1));
     PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
-    const auto* S_rel = reinterpret_cast<const longlong2*>(S.rel);
+    const bool kcol = index && S.columns;   // the probe side's key column itself
+    const auto* S_rel = kcol ? reinterpret_cast<const longlong2*>(S.ckeys) : reinterpret_cast<const longlong2*>(S.rel);
     const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
     const auto* pays = static_cast<const int64_t*>(c->np_pays.p);
     auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
     auto* cnt = static_cast<unsigned long long*>(c->count.p);
     RowsJob J;
     J.nS = S.n;
-    J.s_aos = S_rel;
+    J.s_aos = index ? nullptr : S_rel;
     J.nF = static_cast<uint64_t>(g.nb) * kNPSlots;
     J.tab = tab;
     J.rp = pays;
     J.table_bytes = J.build_bytes = static_cast<uint64_t>(g.nb) * 64;
     J.count_bytes = inner_count_bytes(0, S.n) + J.table_bytes;
+    J.index = index;
+    auto hitp = [&] { return static_cast<JoinedRow*>(c->row_hit.p); };
+    auto index_launch = [&](auto keys, auto h, bool bmark, bool em, IndexSink sink, uint32_t nrows) {
+        constexpr int HK = decltype(h)::value, KEYS = decltype(keys)::value;
+        if (em)
+            hipLaunchKernelGGL((k_np_inner<HK, true, false, IndexSink, KEYS>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
+                               pays, g, p->hash_seed, pairs, cnt, sink, nrows);
+        else if (bmark)
+            hipLaunchKernelGGL((k_np_inner<HK, false, true, JoinedRow*, KEYS>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
+                               pays, g, p->hash_seed, pairs, cnt, hitp(), 0u);
+        else
+            hipLaunchKernelGGL((k_np_inner<HK, false, false, JoinedRow*, KEYS>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
+                               pays, g, p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
+    };
+    auto index_pass = [&](bool bmark, bool em, IndexSink sink, uint32_t nrows) -> int {
+        with_hash(p->hash, [&](auto h) {
+            if (kcol) index_launch(std::integral_constant<int, 1>{}, h, bmark, em, sink, nrows);
+            else index_launch(std::integral_constant<int, 2>{}, h, bmark, em, sink, nrows);
+        });
+        PHJ_LAUNCHED(c, "k_np_inner");
+        return PHJ_OK;
+    };
+    J.emit_index = [&](IndexSink sink, uint32_t nrows) -> int { return index_pass(false, true, sink, nrows); };
     J.count = [&](bool bmark) -> int {
+        if (index) return index_pass(bmark, false, IndexSink{}, 0u);
         with_hash(p->hash, [&](auto h) {
             constexpr int HK = decltype(h)::value;
             // (marking: the flags travel in the count pass's unused row pointer, phj_inner.h)
@@ -2904,16 +2987,27 @@ int join_nopart_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int
     return fill_timers(c, r);
 }
 
+// index (phj_join_indices): both sides' pass 1 synthesises row numbers, and
+// the emit pass stores them into the two index columns.
 int join_radix_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, bool emit,
-                    phj_join_result* r, phj_row_counts* n) {
+                    phj_join_result* r, phj_row_counts* n, bool index = false) {
     const SideState& R = c->side[PHJ_SIDE_BUILD];
     const SideState& S = c->side[PHJ_SIDE_PROBE];
     if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
     if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
     FusedJoin j;
-    PHJ_TRY(fused_setup(c, p, "radix row join", j));
+    PHJ_TRY(fused_setup(c, p, "radix row join", j, index ? PaySrc::RowNumber : PaySrc::Bound));
     auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
     RowsJob J;
+    J.index = index;
+    J.emit_index = [&](IndexSink sink, uint32_t nrows) -> int {
+        with_hash(j.pl.hk, [&](auto h) {
+            hipLaunchKernelGGL((k_inner_fused<decltype(h)::value, true, false, IndexSink>), dim3(j.grid), dim3(kBlock), 0, c->ks,
+                               j.fa, pairs, S.view.payloads, sink, nrows);
+        });
+        PHJ_LAUNCHED(c, "k_inner_fused");
+        return PHJ_OK;
+    };
     J.nS = j.nS;
     J.sk = S.view.keys;
     J.sp = S.view.payloads;
@@ -2947,7 +3041,9 @@ int join_radix_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int6
         return PHJ_OK;
     };
     r->num_partitions = j.requested;
-    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n);
+    // (a key column's pass 1 reads 8 B per tuple less in each of its reads)
+    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n) -
+                           (index && R.columns ? R.n * 16 : 0) - (index && S.columns ? S.n * 16 : 0);
     hipEvent_t p1;
     PHJ_TRY(rows_passes(c, classes, null_payload, emit, J, r, n, &p1));
     return fused_times(c, j, p1, r);
@@ -2955,7 +3051,7 @@ int join_radix_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int6
 
 // An empty side: nothing to join; every tuple of the other side is "only".
 int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, phj_join_result* r,
-                    phj_row_counts* n) {
+                    phj_row_counts* n, bool index = false) {
     const SideState& R = c->side[PHJ_SIDE_BUILD];
     const SideState& S = c->side[PHJ_SIDE_PROBE];
     n->probe_only = (classes & PHJ_ROWS_PROBE_ONLY) ? S.n : 0;   // (at least one of the two is empty)
@@ -2963,28 +3059,37 @@ int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emi
     n->rows = n->probe_only + n->build_only;
     r->matches = n->rows;
     if (!emit || n->rows == 0) return PHJ_OK;
-    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows);
-    PHJ_TRY(ensure(c, c->mat_rows, n->rows * sizeof(JoinedRow)));
+    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows, index);
+    const uint64_t row_bytes = index ? 2 * sizeof(int64_t) : sizeof(JoinedRow);
+    PHJ_TRY(ensure(c, c->mat_rows, n->rows * row_bytes));
     const bool build = n->build_only > 0;
     const SideState& T = build ? R : S;
     hipEvent_t e0, e1;
     PHJ_TRY(mark(c, &e0));
-    PHJ_TRY(timer_begin(c, build ? "rows.build_only" : "rows.emit", n->rows * (16 + 24)));
+    // (the index columns are written from the positions alone: nothing is read)
+    const uint64_t bytes = n->rows * ((index ? 0 : 16) + row_bytes);
+    PHJ_TRY(timer_begin(c, build ? "rows.build_only" : "rows.emit", bytes));
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((T.n + kBlock - 1) / kBlock, 8192));
-    hipLaunchKernelGGL(k_rows_side, dim3(grid), dim3(kBlock), 0, c->ks, reinterpret_cast<const longlong2*>(T.rel), T.n,
-                       null_payload, build, static_cast<JoinedRow*>(c->mat_rows.p));
+    if (index)
+        hipLaunchKernelGGL(k_rows_side<IndexSink>, dim3(grid), dim3(kBlock), 0, c->ks, static_cast<const longlong2*>(nullptr), T.n,
+                           null_payload, build, index_sink(c, n->rows));
+    else
+        hipLaunchKernelGGL(k_rows_side<>, dim3(grid), dim3(kBlock), 0, c->ks, reinterpret_cast<const longlong2*>(T.rel), T.n,
+                           null_payload, build, static_cast<JoinedRow*>(c->mat_rows.p));
     PHJ_LAUNCHED(c, "k_rows_side");
     PHJ_TRY(timer_end(c));
     PHJ_TRY(mark(c, &e1));
     PHJ_HIP(c, hipStreamSynchronize(c->ks));
-    r->algorithmic_bytes = n->rows * (16 + 24);
+    r->algorithmic_bytes = bytes;
     r->probe_ms = r->total_ms = elapsed(c, e0, e1);
     return fill_timers(c, r);
 }
 
 // phj_join_rows_count (emit = false) / phj_join_rows.
+// index: phj_join_indices (emit): keys only, no packed copy, the result in
+// the two index columns.
 int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, phj_join_result* r,
-              phj_row_counts* n, bool emit, const char* what) {
+              phj_row_counts* n, bool emit, const char* what, bool index = false) {
     if (!c || !r || !n) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
     (void)hipGetLastError();
@@ -3000,17 +3105,20 @@ int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t nu
     c->timer_skipped = false;
     c->count_pinned = false;
     reset_timers(c);
-    if (emit) c->mat_n = 0;
+    if (emit) c->mat_n = c->idx_n = 0;   // one result at a time
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
-    PHJ_TRY(need_tuples_both(c, emit, what));   // (sides bound as columns)
+    if (!index) PHJ_TRY(need_tuples_both(c, emit, what));   // (sides bound as columns)
+    for (int side : {PHJ_SIDE_BUILD, PHJ_SIDE_PROBE})
+        if (index && c->side[side].n > 0 && !c->side[side].rel && !c->side[side].columns)
+            return set_err(c, PHJ_ERR_STATE, "relation not bound");
     // decided here: np_build refuses an empty build side, and no table or
     // partition is needed to know that the other side has no partner
     if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0)
-        PHJ_TRY(rows_empty_side(c, classes, null_payload, emit, r, n));
-    else if (p->algo == PHJ_ALGO_NO_PARTITIONING) PHJ_TRY(join_nopart_rows(c, p, classes, null_payload, emit, r, n));
-    else PHJ_TRY(join_radix_rows(c, p, classes, null_payload, emit, r, n));
-    if (emit) c->mat_n = n->rows;
+        PHJ_TRY(rows_empty_side(c, classes, null_payload, emit, r, n, index));
+    else if (p->algo == PHJ_ALGO_NO_PARTITIONING) PHJ_TRY(join_nopart_rows(c, p, classes, null_payload, emit, r, n, index));
+    else PHJ_TRY(join_radix_rows(c, p, classes, null_payload, emit, r, n, index));
+    if (emit) (index ? c->idx_n : c->mat_n) = n->rows;
     return PHJ_OK;
 }
 
@@ -3207,7 +3315,7 @@ void phj_ctx_destroy(phj_ctx* c) {
             free_buf(*b);
     }
     for (DevBuf* b : {&c->ht_tab, &c->ht_desc, &c->r_codes, &c->r_bounds, &c->scan_partials, &c->prep, &c->tkeys, &c->tpays, &c->toffs, &c->gcursor, &c->items, &c->biglist,
-                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->agg_acc, &c->agg_cnt, &c->agg_rows, &c->agg_res, &c->cl_done, &c->hot})
+                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->agg_acc, &c->agg_cnt, &c->agg_rows, &c->agg_res, &c->cl_done, &c->hot, &c->gather_bad})
         free_buf(*b);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     for (hipEvent_t e : {c->hot_fork, c->hot_join})
@@ -3961,7 +4069,7 @@ int phj_join_materialize(phj_ctx* c, const phj_join_params* p, phj_join_result* 
     c->defer_timers = false;
     c->lean_timers = false;
     reset_timers(c);
-    c->mat_n = 0;
+    c->mat_n = c->idx_n = 0;   // (the index columns of phj_join_indices lie in the same buffer)
     PHJ_TRY(need_tuples_both(c, true, "phj_join_materialize"));   // (sides bound as columns)
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) {
         SideState& S = c->side[PHJ_SIDE_PROBE];
@@ -4020,6 +4128,65 @@ int phj_joined_download(phj_ctx* c, phj_joined* host, uint64_t n) {
     PHJ_HIP(c, hipSetDevice(c->device));
     PHJ_HIP(c, hipMemcpyAsync(host, c->mat_rows.p, n * sizeof(phj_joined), hipMemcpyDeviceToHost, c->stream));
     PHJ_HIP(c, hipStreamSynchronize(c->stream));
+    return PHJ_OK;
+}
+
+// ---- row-number joins (phj_index.h) ----
+
+int phj_join_indices(phj_ctx* c, const phj_join_params* p, uint32_t classes, phj_join_result* r, phj_row_counts* n) {
+    return join_rows(c, p, classes, PHJ_NO_ROW, r, n, true, "phj_join_indices", true);
+}
+
+int phj_joined_indices(phj_ctx* c, const int64_t** build_rows, const int64_t** probe_rows, uint64_t* n) {
+    if (!c) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_joined_indices: single-device contexts only");
+    const IndexSink s = index_sink(c, c->idx_n);
+    if (build_rows) *build_rows = c->idx_n ? s.build_rows : nullptr;
+    if (probe_rows) *probe_rows = c->idx_n ? s.probe_rows : nullptr;
+    if (n) *n = c->idx_n;
+    return PHJ_OK;
+}
+
+int phj_joined_indices_download(phj_ctx* c, int64_t* build_rows, int64_t* probe_rows, uint64_t n) {
+    if (!c) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_joined_indices_download: single-device contexts only");
+    if (n > c->idx_n) return set_err(c, PHJ_ERR_RANGE, "more rows requested than the last index join made");
+    if (n == 0) return PHJ_OK;
+    PHJ_HIP(c, hipSetDevice(c->device));
+    const IndexSink s = index_sink(c, c->idx_n);
+    // (hipMemcpyDefault: the destinations may be host or device memory)
+    if (build_rows) PHJ_HIP(c, hipMemcpyAsync(build_rows, s.build_rows, n * 8, hipMemcpyDefault, c->stream));
+    if (probe_rows) PHJ_HIP(c, hipMemcpyAsync(probe_rows, s.probe_rows, n * 8, hipMemcpyDefault, c->stream));
+    PHJ_HIP(c, hipStreamSynchronize(c->stream));
+    return PHJ_OK;
+}
+
+int phj_gather_column(phj_ctx* c, const int64_t* src, uint64_t src_n, const int64_t* idx, uint64_t n,
+                      const int64_t* null_value, int64_t* out) {
+    if (!c) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_gather_column: single-device contexts only");
+    (void)hipGetLastError();
+    if (n == 0) return PHJ_OK;
+    if (!idx || !out || (src_n && !src)) return set_err(c, PHJ_ERR_INVALID, "null argument");
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(out)) & 7)
+        return set_err(c, PHJ_ERR_INVALID, "phj_gather_column: columns need 8-byte alignment");
+    if (src_n >= (1ull << 63)) return set_err(c, PHJ_ERR_RANGE, "phj_gather_column: src_n above 2^63");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(ensure(c, c->gather_bad, 8));
+    auto* bad = static_cast<unsigned long long*>(c->gather_bad.p);
+    PHJ_HIP(c, hipMemsetAsync(bad, 0, 8, c->stream));
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n + kBlock - 1) / kBlock, static_cast<uint64_t>(c->num_cus) * 32));
+    if (null_value)
+        hipLaunchKernelGGL(k_gather_column<false>, dim3(grid), dim3(kBlock), 0, c->stream, src, src_n, idx, n, *null_value, out, bad);
+    else
+        hipLaunchKernelGGL(k_gather_column<true>, dim3(grid), dim3(kBlock), 0, c->stream, src, src_n, idx, n, int64_t{0}, out, bad);
+    PHJ_LAUNCHED(c, "k_gather_column");
+    unsigned long long h = 0;
+    PHJ_HIP(c, hipMemcpyAsync(&h, bad, 8, hipMemcpyDeviceToHost, c->stream));
+    PHJ_HIP(c, hipStreamSynchronize(c->stream));
+    if (h)
+        return set_err(c, PHJ_ERR_RANGE, "phj_gather_column: " + std::to_string(h) + " indices outside [0, " +
+                                             std::to_string(src_n) + ") other than PHJ_NO_ROW: not dereferenced, given the null treatment");
     return PHJ_OK;
 }
 

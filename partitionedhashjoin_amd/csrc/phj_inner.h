@@ -17,6 +17,8 @@
 // 2^32 pairs (then no block sum can have wrapped either).
 #pragma once
 
+#include <type_traits>
+
 #include "phj_mat.h"
 
 // A/B builds only (make build/libphj_NAME.so HIPDEFS=-DPHJ_INNER_COOP=0): the
@@ -31,6 +33,33 @@ constexpr uint32_t kInnerWide = 64;   // k_inner_fused: bucket length from which
 constexpr uint32_t kInnerWideLanes = 16;   // ... count pass: only while at most this many lanes have such a bucket
 constexpr uint32_t kInnerHitBit = 0x80000000u;   // k_inner_fused, BMARK: lr[pos] = in-round index | this once compared equal
 
+// Where an emitting kernel stores a row: the 24-B rows of phj_join_inner /
+// phj_join_rows (JoinedRow*), or the two index columns of phj_join_indices
+// (phj_index.h), whose joins carry row numbers as payloads: build_rows[at] and
+// probe_rows[at], no id and no 24-B row. The sink is a template parameter
+// whose default is the row pointer, so the instantiations of the row joins
+// keep their arguments and their code.
+struct IndexSink {
+    int64_t* build_rows;
+    int64_t* probe_rows;
+};
+
+__device__ __forceinline__ void put_row(JoinedRow* out, uint32_t at, int64_t id, int64_t pa, int64_t pb) {
+    JoinedRow r;
+    r.id = id;
+    r.payload_a = pa;
+    r.payload_b = pb;
+    out[at] = r;
+}
+
+__device__ __forceinline__ void put_row(const IndexSink& out, uint32_t at, int64_t, int64_t pa, int64_t pb) {
+    out.build_rows[at] = pa;
+    out.probe_rows[at] = pb;
+}
+
+template <class SINK>
+constexpr bool kIndexSink = std::is_same<SINK, IndexSink>::value;
+
 // BMARK (the count pass of phj_join_rows with build-only rows, phj_outer.h):
 // the join also says which build tuples met an equal probe key, one byte per
 // build tuple, cleared by the host before the launch. A flag is only ever
@@ -44,9 +73,9 @@ constexpr uint32_t kInnerHitBit = 0x80000000u;   // k_inner_fused, BMARK: lr[pos
 // key; EMIT: their rows from out[row] on; BMARK: hit[b * kNPSlots + s] = 1 for
 // each (tested first: a hot key's run is walked by thousands of probe tuples,
 // whose steady state is then cached reads). Returns how many.
-template <bool EMIT, bool BMARK>
+template <bool EMIT, bool BMARK, class SINK = JoinedRow*>
 __device__ __forceinline__ uint32_t np_bucket_pairs(const longlong2 (&q)[4], uint32_t b, int64_t key,
-                                                    const int64_t* pays, int64_t pb, JoinedRow* out, uint32_t row,
+                                                    const int64_t* pays, int64_t pb, SINK out, uint32_t row,
                                                     uint32_t nrows, uint8_t* hit) {
     int64_t ks[kNPSlots];
     const uint32_t fill = np_unpack(q, ks);
@@ -55,13 +84,7 @@ __device__ __forceinline__ uint32_t np_bucket_pairs(const longlong2 (&q)[4], uin
 #pragma unroll
     for (int s = 0; s < kNPSlots; s++) {
         if (static_cast<uint32_t>(s) < c && ks[s] == key) {
-            if (EMIT && row + n < nrows) {
-                JoinedRow r;
-                r.id = key;
-                r.payload_a = pays[static_cast<size_t>(b) * kNPSlots + s];
-                r.payload_b = pb;
-                out[row + n] = r;
-            }
+            if (EMIT && row + n < nrows) put_row(out, row + n, key, pays[static_cast<size_t>(b) * kNPSlots + s], pb);
             if (BMARK) {
                 uint8_t* f = hit + static_cast<size_t>(b) * kNPSlots + s;
                 if (*f == 0) *f = 1;
@@ -82,21 +105,49 @@ __device__ __forceinline__ uint32_t np_bucket_pairs(const longlong2 (&q)[4], uin
 //               not stored (the count pass saw the same table: there are none).
 // BMARK (EMIT = false only): out holds the hit flags of the table's slots,
 //               indexed like pays (b * kNPSlots + s).
-template <int HK, bool EMIT, bool BMARK = false>
+// KEYS != 0 (phj_join_indices): S is read for its keys alone, in both passes,
+// and probe tuple i's payload is i. KEYS = 1: S is a key column (int64 at
+// stride 8, any 8-byte aligned base); KEYS = 2: 16-B tuples, their ids read at
+// stride 16.
+template <int HK, int KEYS, int IT>
+__device__ __forceinline__ void np_probe_front_keys(const longlong2* S, uint64_t nS, uint64_t base, const NPBucket* tab,
+                                                    NPHome g, uint64_t seed, longlong2 (&t)[IT], uint32_t (&b)[IT],
+                                                    longlong2 (&q)[IT][4]) {
+    static_assert(KEYS == 1 || KEYS == 2, "1: key column, 2: tuples");
+    const int64_t* K = reinterpret_cast<const int64_t*>(S);
+#pragma unroll
+    for (int j = 0; j < IT; j++) {
+        const uint64_t i = base + static_cast<uint64_t>(j) * kBlock + threadIdx.x;
+        t[j].x = i < nS ? __builtin_nontemporal_load(K + i * KEYS) : 0;
+        t[j].y = static_cast<int64_t>(i);
+    }
+#pragma unroll
+    for (int j = 0; j < IT; j++) {
+        b[j] = np_home_r(hash64<HK>(static_cast<uint64_t>(t[j].x), seed), g);
+        const longlong2* bp = reinterpret_cast<const longlong2*>(tab + b[j]);
+#pragma unroll
+        for (int w = 0; w < 4; w++) q[j][w] = bp[w];
+    }
+}
+
+template <int HK, bool EMIT, bool BMARK = false, class SINK = JoinedRow*, int KEYS = 0>
 __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_t nS, const NPBucket* tab,
                                                      const int64_t* pays, NPHome g, uint64_t seed, uint32_t* pairs,
-                                                     unsigned long long* count, JoinedRow* out, uint32_t nrows) {
+                                                     unsigned long long* count, SINK out, uint32_t nrows) {
     static_assert(!(EMIT && BMARK), "hit flags are written by the count pass");
+    static_assert(!BMARK || !kIndexSink<SINK>, "the hit flags travel in the row pointer");
     __shared__ unsigned long long red[kWaves];
     constexpr int IT = 4;   // as k_np_probe: every home bucket of a round requested before any compare
-    uint8_t* hit = BMARK ? reinterpret_cast<uint8_t*>(out) : nullptr;
+    uint8_t* hit = nullptr;
+    if constexpr (BMARK) hit = reinterpret_cast<uint8_t*>(out);
     unsigned long long total = 0;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock * IT;
     for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kBlock * IT; base < nS; base += stride) {
         longlong2 t[IT];
         uint32_t b[IT];
         longlong2 q[IT][4];
-        np_probe_front<HK, EMIT>(S, nS, base, tab, g, seed, t, b, q);
+        if constexpr (KEYS != 0) np_probe_front_keys<HK, KEYS>(S, nS, base, tab, g, seed, t, b, q);
+        else np_probe_front<HK, EMIT>(S, nS, base, tab, g, seed, t, b, q);
 #pragma unroll
         for (int j = 0; j < IT; j++) {
             const uint64_t i = base + static_cast<uint64_t>(j) * kBlock + threadIdx.x;
@@ -152,12 +203,16 @@ __global__ __launch_bounds__(kBlock) void k_np_inner(const longlong2* S, uint64_
 //               compared equal there (either compare path), kInnerHitBit;
 //               after the round's probe loop each lane turns its RPL
 //               positions' bits into the flags of build rows rlo + r0 + index.
-template <int HK, bool EMIT, bool BMARK = false>
+// SINK = IndexSink (phj_join_indices, EMIT only): the payloads both sides
+// carry are row numbers and go to the two index columns; the wide path's 64
+// consecutive rows are then two contiguous 512-B stores.
+template <int HK, bool EMIT, bool BMARK = false, class SINK = JoinedRow*>
 __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* pairs, const int64_t* spays,
-                                                        JoinedRow* out, uint32_t nrows) {
+                                                        SINK out, uint32_t nrows) {
     constexpr int TCAP = 256, RPL = TCAP / 64, OCAP = TCAP / 2 + 1, KPL = 4;
     constexpr uint32_t SUB = 64 * KPL;
     static_assert(!(EMIT && BMARK), "hit flags are written by the count pass");
+    static_assert(EMIT || !kIndexSink<SINK>, "the count pass stores no rows");
     __shared__ int64_t lk_all[kWaves][TCAP];
     __shared__ uint32_t lr_all[kWaves][TCAP];
     __shared__ uint32_t lo_all[kWaves][OCAP];
@@ -168,7 +223,8 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
     uint32_t* lr = lr_all[wave];
     uint32_t* loffs = lo_all[wave];
     uint32_t* lcur = cur_all[wave];
-    uint8_t* hitf = BMARK ? reinterpret_cast<uint8_t*>(out) : nullptr;
+    uint8_t* hitf = nullptr;
+    if constexpr (BMARK) hitf = reinterpret_cast<uint8_t*>(out);
     const int64_t* rkeys = a.L.seg[0].keys;
     const int64_t* rpays = a.L.seg[0].pays;
     const uint32_t* rb = a.L.seg[0].bounds;
@@ -262,13 +318,7 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
                                         row = pairs[s];
                                         pb = spays[s];
                                     }
-                                    if (row + n < nrows) {
-                                        JoinedRow r;
-                                        r.id = key;
-                                        r.payload_a = rpays[lr[t]];
-                                        r.payload_b = pb;
-                                        out[row + n] = r;
-                                    }
+                                    if (row + n < nrows) put_row(out, row + n, key, rpays[lr[t]], pb);
                                 }
                                 if (BMARK) {   // (lanes on one hot key store the same word)
                                     const uint32_t v = lr[t];
@@ -292,13 +342,7 @@ __global__ __launch_bounds__(kBlock) void k_inner_fused(FusedArgs a, uint32_t* p
                             const uint64_t bal = __ballot(hit);
                             if (EMIT && hit) {   // 64 consecutive rows: one contiguous 1.5 KB store
                                 const uint32_t at = wrow + wn + __popcll(bal & ((1ull << lane) - 1ull));
-                                if (at < nrows) {
-                                    JoinedRow r;
-                                    r.id = wkey;
-                                    r.payload_a = rpays[lr[t]];
-                                    r.payload_b = wpb;
-                                    out[at] = r;
-                                }
+                                if (at < nrows) put_row(out, at, wkey, rpays[lr[t]], wpb);
                             }
                             if (BMARK && hit) {
                                 const uint32_t v = lr[t];

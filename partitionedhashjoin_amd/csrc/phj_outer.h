@@ -52,41 +52,58 @@ __global__ __launch_bounds__(kBlock) void k_rows_map(uint32_t* pairs, uint64_t n
 // The null row {id, null_payload, payload_b} of every probe tuple flagged in
 // only[], at the tuple's first row first[i] (the scanned pairs[]). The probe
 // side is AoS tuples (sk == nullptr: s_aos) or SoA columns (sk, sp).
+// SINK = IndexSink (phj_join_indices): the row is {null_payload, the tuple's
+// row number}: sp[i], the number the radix join's partitioning carried, or i
+// itself when sp is null (NoPartitioning: storage order is input order). No
+// key is read.
+template <class SINK = JoinedRow*>
 __global__ __launch_bounds__(kBlock) void k_rows_fill(const uint64_t* only, const uint32_t* first, uint64_t n,
                                                       const longlong2* s_aos, const int64_t* sk, const int64_t* sp,
-                                                      int64_t null_payload, JoinedRow* out, uint32_t nrows) {
+                                                      int64_t null_payload, SINK out, uint32_t nrows) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
         if (!((only[i >> 6] >> (i & 63)) & 1)) continue;
         const uint32_t row = first[i];
         if (row >= nrows) continue;
-        JoinedRow r;
-        if (sk) {
-            r.id = sk[i];
-            r.payload_b = sp[i];
+        if constexpr (kIndexSink<SINK>) {
+            put_row(out, row, 0, null_payload, sp ? sp[i] : static_cast<int64_t>(i));
         } else {
-            const longlong2 t = s_aos[i];
-            r.id = t.x;
-            r.payload_b = t.y;
+            JoinedRow r;
+            if (sk) {
+                r.id = sk[i];
+                r.payload_b = sp[i];
+            } else {
+                const longlong2 t = s_aos[i];
+                r.id = t.x;
+                r.payload_b = t.y;
+            }
+            r.payload_a = null_payload;
+            out[row] = r;
         }
-        r.payload_a = null_payload;
-        out[row] = r;
     }
 }
 
 // An empty other side: every tuple of rel is "only", its row out[i] in input
 // order. build: rel is the build side ({id, payload, null}), else the probe
 // side ({id, null, payload}).
+// SINK = IndexSink (phj_join_indices): row i is {i, null} or {null, i}; rel is
+// not read (it may be null: a side bound as columns).
+template <class SINK = JoinedRow*>
 __global__ __launch_bounds__(kBlock) void k_rows_side(const longlong2* rel, uint64_t n, int64_t null_payload,
-                                                      bool build, JoinedRow* out) {
+                                                      bool build, SINK out) {
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) {
-        const longlong2 t = rel[i];
-        JoinedRow r;
-        r.id = t.x;
-        r.payload_a = build ? t.y : null_payload;
-        r.payload_b = build ? null_payload : t.y;
-        out[i] = r;
+        if constexpr (kIndexSink<SINK>) {
+            const int64_t me = static_cast<int64_t>(i);
+            put_row(out, static_cast<uint32_t>(i), 0, build ? me : null_payload, build ? null_payload : me);
+        } else {
+            const longlong2 t = rel[i];
+            JoinedRow r;
+            r.id = t.x;
+            r.payload_a = build ? t.y : null_payload;
+            r.payload_b = build ? null_payload : t.y;
+            out[i] = r;
+        }
     }
 }
 
@@ -127,11 +144,13 @@ __global__ __launch_bounds__(kBlock) void k_build_only_count(const uint8_t* hit,
 // ballots inside the block). NP: keys from the table's slots, payloads
 // pays[i]; else keys[i], pays[i]. Rows from nrows on are not stored (the
 // count kernel saw the same flags: there are none).
-template <bool NP>
+// SINK = IndexSink (phj_join_indices): {pays[i], null_payload}, pays[i] being
+// the build tuple's row number; no key is read.
+template <bool NP, class SINK = JoinedRow*>
 __global__ __launch_bounds__(kBlock) void k_build_only_write(const uint8_t* hit, const NPBucket* tab, uint64_t n,
                                                              const int64_t* keys, const int64_t* pays,
                                                              int64_t null_payload, const uint32_t* offs,
-                                                             JoinedRow* out, uint32_t row0, uint32_t nrows) {
+                                                             SINK out, uint32_t row0, uint32_t nrows) {
     __shared__ uint32_t wcnt[kWaves];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kMatBlock;
@@ -152,11 +171,15 @@ __global__ __launch_bounds__(kBlock) void k_build_only_write(const uint8_t* hit,
         }
         const uint32_t at = row + wbase + before;
         if (lone && at < nrows) {
-            JoinedRow r;
-            r.id = NP ? tab[i / kNPSlots].key[i % kNPSlots] : keys[i];
-            r.payload_a = pays[i];
-            r.payload_b = null_payload;
-            out[at] = r;
+            if constexpr (kIndexSink<SINK>) {
+                put_row(out, at, 0, pays[i], null_payload);
+            } else {
+                JoinedRow r;
+                r.id = NP ? tab[i / kNPSlots].key[i % kNPSlots] : keys[i];
+                r.payload_a = pays[i];
+                r.payload_b = null_payload;
+                out[at] = r;
+            }
         }
         row += total;
         __syncthreads();   // wcnt reused by the next round

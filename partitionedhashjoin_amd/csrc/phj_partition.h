@@ -300,6 +300,17 @@ __device__ __forceinline__ void load_tuple(const PassArgs& a, uint32_t idx, int6
     }
 }
 
+// Pass 1 of the row-number joins (phj_index.h): the payload is not loaded but
+// synthesised, the element's position idx in the bound relation. ROWS 1: the
+// relation is a key column (8 B per tuple); ROWS 2: 16-B tuples whose .payload
+// is never read.
+template <int ROWS>
+__device__ __forceinline__ void load_key_row(const PassArgs& a, uint32_t idx, int64_t& k, int64_t& p) {
+    static_assert(ROWS == 1 || ROWS == 2, "1: key column, 2: tuples");
+    k = a.in_keys[static_cast<size_t>(idx) * ROWS];
+    p = static_cast<int64_t>(idx);
+}
+
 template <bool OUT_AOS>
 __device__ __forceinline__ void store_tuple(const PassArgs& a, uint32_t o, int64_t k, int64_t p) {
     if constexpr (OUT_AOS) {
@@ -333,7 +344,11 @@ __device__ __forceinline__ void store_next_digit(const PassArgs& a, uint32_t o, 
 }
 
 // Per-tile digit histogram -> hist[(tb_s * nbins) + d * ntiles_s + tseg].
-template <int BLOCK, int ITEMS, bool AOS, int HK>
+// KCOL (pass 1 of the row-number joins, phj_index.h, over a caller's key
+// column): one 8-B load per key, so a column at an 8-byte aligned base is read
+// inside [lo, hi) and nowhere else (the pair loads of the SoA form below start
+// at an even element and may end one past hi).
+template <int BLOCK, int ITEMS, bool AOS, int HK, bool KCOL = false>
 __global__ __launch_bounds__(BLOCK) void k_hist(PassArgs a) {
     __builtin_amdgcn_s_setprio(3);   // (R's chain beside S's persistent pass 1: issue first)
     constexpr int NW = BLOCK / 64;
@@ -349,14 +364,15 @@ __global__ __launch_bounds__(BLOCK) void k_hist(PassArgs a) {
     // Order does not matter for a histogram, so every lane loads 16 B (one AoS
     // tuple, or two consecutive keys of a SoA key column: aligned pairs) and
     // counts into its wave's private LDS row (count_digit).
-    if constexpr (AOS) {
+    if constexpr (AOS || KCOL) {
         const uint32_t cnt = L.hi - L.lo;
         int64_t key[ITEMS];
         const uint32_t wbase = wave * 64 * ITEMS;
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
             const uint32_t e = wbase + i * 64 + lane;
-            key[i] = e < cnt ? reinterpret_cast<const longlong2*>(a.in_keys)[L.lo + e].x : 0;
+            if constexpr (KCOL) key[i] = e < cnt ? a.in_keys[L.lo + e] : 0;
+            else key[i] = e < cnt ? reinterpret_cast<const longlong2*>(a.in_keys)[L.lo + e].x : 0;
         }
         __syncthreads();
 #pragma unroll
@@ -477,7 +493,9 @@ struct SortedDigits {
 };
 
 // Stable scatter of one tile using the scanned offsets.
-template <int BLOCK, int ITEMS, bool AOS, bool OUT_AOS, int HK>
+// ROWS != 0: load_key_row (the payload is the element's index L.lo + e in the
+// relation, never a function of blockIdx: xcd_remap reorders the tiles).
+template <int BLOCK, int ITEMS, bool AOS, bool OUT_AOS, int HK, int ROWS = 0>
 __global__ __launch_bounds__(BLOCK) void k_scatter(PassArgs a) {
     constexpr int NW = BLOCK / 64;
     constexpr int T = BLOCK * ITEMS;
@@ -508,7 +526,10 @@ __global__ __launch_bounds__(BLOCK) void k_scatter(PassArgs a) {
         const uint32_t e = wbase + i * 64 + lane;
         key[i] = 0;
         pay[i] = 0;
-        if (e < cnt) load_tuple<AOS>(a, L.lo + e, key[i], pay[i]);
+        if (e < cnt) {
+            if constexpr (ROWS != 0) load_key_row<ROWS>(a, L.lo + e, key[i], pay[i]);
+            else load_tuple<AOS>(a, L.lo + e, key[i], pay[i]);
+        }
     }
     __syncthreads();
     // stable ranking: wave-major, then round i, then lane
@@ -608,7 +629,8 @@ __global__ __launch_bounds__(BLOCK) void k_scatter(PassArgs a) {
 // 16-B tuples (one ds_write_b128 / ds_read_b128 per tuple instead of two
 // 8-B column accesses). The host launches VAR 3; the keys-only hash-code form
 // the counting probe consumes is k_chunk_codes below.
-template <int BLOCK, int ITEMS, int HK, int VAR = 0>
+// ROWS != 0 (the row-number joins): load_key_row's input forms.
+template <int BLOCK, int ITEMS, int HK, int VAR = 0, int ROWS = 0>
 __global__ __launch_bounds__(BLOCK)
 __attribute__((amdgpu_waves_per_eu((BLOCK * ITEMS <= 4096 ? 2 : 1) * BLOCK / 256)))   // what the LDS lets share a CU
 void k_scatter_chunked(PassArgs a, uint32_t ntiles, uint32_t per) {
@@ -661,7 +683,9 @@ void k_scatter_chunked(PassArgs a, uint32_t ntiles, uint32_t per) {
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
             const uint32_t ix = min(lo + wbase + i * 64 + lane, a.n - 1);
-            if (a.nt_load) {
+            if constexpr (ROWS != 0) {
+                load_key_row<ROWS>(a, ix, key[i], pay[i]);
+            } else if (a.nt_load) {
                 typedef long long v2i __attribute__((ext_vector_type(2)));
                 const v2i v = __builtin_nontemporal_load(reinterpret_cast<const v2i*>(rel) + ix);
                 key[i] = v.x;

@@ -27,6 +27,11 @@
 // GpuConfiguration::Columns binds both relations as key / payload columns
 // (phj_relation_to_columns) before whatever was asked for runs; the results'
 // `layout` says which binding ran.
+// GpuConfiguration::RowsAsIndices makes the rows of RowClasses / MaterializeAll
+// another way (internal::join_by_indices): the key columns alone stay bound,
+// phj_join_indices returns (build row, probe row) pairs and phj_gather_column
+// composes the JoinedTuple columns from them; the results' `rows_as` says
+// which way ran.
 // C ABI errors surface as std::runtime_error / std::invalid_argument, which the
 // CLI catches and turns into exit(1) (src/main.cpp:277-281).
 #pragma once
@@ -53,7 +58,7 @@ namespace Gpu {
 // The reference's thread pool (src/main.cpp:235-241) sits in this slot.
 class Device {
    public:
-    explicit Device(int device = 0) {
+    explicit Device(int device = 0) : m_device(device) {
         const int rc = phj_ctx_create_device(device, &m_ctx);
         if (rc != PHJ_OK) throw std::runtime_error("phj_ctx_create_device(" + std::to_string(device) + ") failed");
     }
@@ -64,6 +69,7 @@ class Device {
         m_gpus = static_cast<int>(devices.size());
     }
     int NumberOfGpus() const { return m_gpus; }
+    int DeviceId() const { return m_device; }   // of a single-device context
     ~Device() { phj_ctx_destroy(m_ctx); }
     Device(const Device&) = delete;
     Device& operator=(const Device&) = delete;
@@ -84,12 +90,71 @@ class Device {
    private:
     phj_ctx* m_ctx = nullptr;
     int m_gpus = 1;
+    int m_device = 0;
 };
 
 namespace internal {
 
 inline std::chrono::nanoseconds ms_to_ns(double ms) {
     return std::chrono::nanoseconds(static_cast<int64_t>(std::llround(ms * 1e6)));
+}
+
+// --rows indices: the rows of the join kind `classes` without a payload ever
+// entering the join. Both relations are split into columns and only the key
+// columns stay bound; phj_join_indices gives (build row, probe row) pairs;
+// three gathers and a coalesce compose the rows' columns on the device:
+//   payloadA = R.payload[build_rows], payloadB = S.payload[probe_rows] (null
+//   where the side is missing), id = S.key[probe_rows], then R.key[build_rows]
+//   into the same column with no null value (it keeps what the first wrote).
+// The C ABI has no allocator: the three result columns are the columns of a
+// scratch context's relations on the same device, read back as tuples.
+inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join_by_indices(Device& dev, const phj_join_params& p,
+                                                                           phj_join_result& r, uint32_t classes,
+                                                                           int64_t null_payload, phj_row_counts& n) {
+    phj_ctx* c = dev.Get();
+    const int64_t *rk = nullptr, *rp = nullptr, *sk = nullptr, *sp = nullptr;
+    uint64_t nR = 0, nS = 0;
+    dev.Check(phj_relation_to_columns(c, PHJ_SIDE_BUILD, 1));
+    dev.Check(phj_relation_to_columns(c, PHJ_SIDE_PROBE, 1));
+    dev.Check(phj_relation_columns(c, PHJ_SIDE_BUILD, &rk, &rp, &nR));
+    dev.Check(phj_relation_columns(c, PHJ_SIDE_PROBE, &sk, &sp, &nS));
+    if ((nR && !rp) || (nS && !sp)) throw std::runtime_error("--rows indices: a relation has no payload column to gather");
+    // (the columns are context-owned and stay where they are: the join sees the keys alone)
+    dev.Check(phj_relation_bind_columns(c, PHJ_SIDE_BUILD, rk, nullptr, nR));
+    dev.Check(phj_relation_bind_columns(c, PHJ_SIDE_PROBE, sk, nullptr, nS));
+    dev.Check(phj_join_indices(c, &p, classes, &r, &n));
+    auto out = std::make_shared<Common::Table<Common::JoinedTuple>>(n.rows, Common::generate_uuid());
+    if (n.rows == 0) return out;
+    const int64_t *brows = nullptr, *prows = nullptr;
+    uint64_t rows = 0;
+    dev.Check(phj_joined_indices(c, &brows, &prows, &rows));
+    if (rows != n.rows) throw std::runtime_error("phj_joined_indices: row count differs from the join's");
+    Device scratch(dev.DeviceId());
+    {
+        const std::vector<int64_t> zeros(rows, 0);
+        scratch.Check(phj_relation_upload_columns(scratch.Get(), PHJ_SIDE_BUILD, zeros.data(), zeros.data(), rows));
+        scratch.Check(phj_relation_upload_columns(scratch.Get(), PHJ_SIDE_PROBE, zeros.data(), nullptr, rows));
+    }
+    const int64_t *id_c = nullptr, *pa_c = nullptr, *pb_c = nullptr;
+    scratch.Check(phj_relation_columns(scratch.Get(), PHJ_SIDE_BUILD, &id_c, &pa_c, nullptr));
+    scratch.Check(phj_relation_columns(scratch.Get(), PHJ_SIDE_PROBE, &pb_c, nullptr, nullptr));
+    int64_t* id = const_cast<int64_t*>(id_c);
+    int64_t* pa = const_cast<int64_t*>(pa_c);
+    int64_t* pb = const_cast<int64_t*>(pb_c);
+    const int64_t zero = 0;
+    dev.Check(phj_gather_column(c, rp, nR, brows, rows, &null_payload, pa));
+    dev.Check(phj_gather_column(c, sp, nS, prows, rows, &null_payload, pb));
+    dev.Check(phj_gather_column(c, sk, nS, prows, rows, &zero, id));
+    dev.Check(phj_gather_column(c, rk, nR, brows, rows, nullptr, id));
+    std::vector<phj_tuple> t(rows);
+    scratch.Check(phj_relation_download(scratch.Get(), PHJ_SIDE_BUILD, t.data(), rows));
+    for (uint64_t i = 0; i < rows; i++) {
+        (*out)[i].id = t[i].id;
+        (*out)[i].payloadA = t[i].payload;
+    }
+    scratch.Check(phj_relation_download(scratch.Get(), PHJ_SIDE_PROBE, t.data(), rows));
+    for (uint64_t i = 0; i < rows; i++) (*out)[i].payloadB = t[i].id;
+    return out;
 }
 
 // phj_join or, with rows requested, phj_join_materialize (one row per matching
@@ -122,11 +187,20 @@ inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, con
         }
         return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());
     }
+    if (gpu.RowsAsIndices && all) {
+        phj_row_counts n{};
+        return join_by_indices(dev, p, r, PHJ_ROWS_PAIRS, gpu.NullPayload, n);
+    }
     if (gpu.RowClasses != 0) {
         phj_row_counts n{};
-        dev.Check(phj_join_rows(dev.Get(), &p, gpu.RowClasses, gpu.NullPayload, &r, &n));
-        auto out = std::make_shared<Common::Table<Common::JoinedTuple>>(n.rows, Common::generate_uuid());
-        dev.Check(phj_joined_download(dev.Get(), reinterpret_cast<phj_joined*>(out->Data()), n.rows));
+        std::shared_ptr<Common::Table<Common::JoinedTuple>> out;
+        if (gpu.RowsAsIndices) {
+            out = join_by_indices(dev, p, r, gpu.RowClasses, gpu.NullPayload, n);
+        } else {
+            dev.Check(phj_join_rows(dev.Get(), &p, gpu.RowClasses, gpu.NullPayload, &r, &n));
+            out = std::make_shared<Common::Table<Common::JoinedTuple>>(n.rows, Common::generate_uuid());
+            dev.Check(phj_joined_download(dev.Get(), reinterpret_cast<phj_joined*>(out->Data()), n.rows));
+        }
         timer.AddResult("pairs", std::to_string(n.pairs));
         timer.AddResult("probe_only", std::to_string(n.probe_only));
         timer.AddResult("build_only", std::to_string(n.build_only));
@@ -151,13 +225,15 @@ inline void apply_layout(Device& dev, const Common::GpuConfiguration& gpu) {
     dev.Check(phj_relation_to_columns(dev.Get(), PHJ_SIDE_PROBE, 1));
 }
 
-inline void add_device_results(Common::IHashJoinTimer& timer, const phj_join_result& r, int gpus, bool columns = false) {
+inline void add_device_results(Common::IHashJoinTimer& timer, const phj_join_result& r, int gpus, bool columns = false,
+                               bool indices = false) {
     timer.AddResult("matches", std::to_string(r.matches));
     timer.AddResult("gpus", std::to_string(gpus));
     timer.AddResult("exchange_us", std::to_string(static_cast<int64_t>(std::llround(r.exchange_ms * 1e3))));
     timer.AddResult("device_total_us", std::to_string(static_cast<int64_t>(std::llround(r.total_ms * 1e3))));
     timer.AddResult("algorithmic_bytes", std::to_string(r.algorithmic_bytes));
     timer.AddResult("layout", columns ? "columns" : "tuples");
+    timer.AddResult("rows_as", indices ? "indices" : "payloads");
 }
 
 }  // namespace internal
@@ -217,7 +293,7 @@ class HashJoiner {
         timer->SetPartitionPhaseDuration(internal::ms_to_ns(r.partition_ms));
         timer->SetBuildPhaseDuration(internal::ms_to_ns(r.build_ms));
         timer->SetProbePhaseDuration(internal::ms_to_ns(r.probe_ms));
-        internal::add_device_results(*timer, r, m_device->NumberOfGpus(), m_gpu.Columns);
+        internal::add_device_results(*timer, r, m_device->NumberOfGpus(), m_gpu.Columns, m_gpu.RowsAsIndices);
         timer->AddResult("partitions", std::to_string(r.num_partitions));
         m_joined = r.matches;
         m_last = r;
@@ -285,7 +361,7 @@ class HashJoiner {
         // the reference's probe figure runs from the build start (Results.hpp:202)
         timer->SetProbePhaseDuration(internal::ms_to_ns(r.build_ms + r.probe_ms));
         timer->SetPartitionPhaseDuration(std::chrono::nanoseconds(0));
-        internal::add_device_results(*timer, r, m_device->NumberOfGpus(), m_gpu.Columns);
+        internal::add_device_results(*timer, r, m_device->NumberOfGpus(), m_gpu.Columns, m_gpu.RowsAsIndices);
         timer->AddResult("probe_only_us", std::to_string(static_cast<int64_t>(std::llround(r.probe_ms * 1e3))));
         m_joined = r.matches;
         m_last = r;

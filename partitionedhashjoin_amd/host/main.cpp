@@ -19,6 +19,7 @@
 //   --join-kind K         inner|probe-outer|build-outer|full-outer|probe-anti|build-anti: return that kind's rows
 //   --aggregate A         totals|groups: report the join's aggregates instead of rows
 //   --layout L            tuples|columns: bind the relations as {id, payload} tuples or as key / payload columns
+//   --rows W              payloads|indices: how the returned rows are made (indices: an index join on the key columns, then gathers)
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -79,6 +80,10 @@ const char* kHelp =
     "                                      into a key and a payload column on the device (phj_relation_to_columns)\n"
     "                                      before the join; the counting join then reads the key columns only.\n"
     "                                      One device only.\n"
+    "  --rows arg (=payloads)              payloads | indices: how the rows of a join kind or of the inner join are made.\n"
+    "                                      indices: both relations are split into columns, only the key columns\n"
+    "                                      stay bound, phj_join_indices returns (build row, probe row) pairs and\n"
+    "                                      phj_gather_column composes the rows from them. One device only.\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
@@ -113,7 +118,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
     static const std::set<std::string> known = {"help", "primary", "secondary", "skew", "log", "join", "format",
                                                 "unit", "output", "filename", "partitions", "device", "gpus", "devices", "exchange", "hash",
                                                 "radix-bits", "seed", "hash-seed", "generate", "table-ratio",
-                                                "materialize", "join-kind", "aggregate", "layout"};
+                                                "materialize", "join-kind", "aggregate", "layout", "rows"};
     Common::Configuration c{};
     c.OutputFormatConfig.TimeUnit = "ms";
     c.OutputConfig.File.Name = "hashjoin.txt";
@@ -189,6 +194,11 @@ Common::Configuration parseArguments(int argc, char** argv) {
             else if (vm["layout"] != "tuples")
                 throw std::invalid_argument("the argument ('" + vm["layout"] + "') for option '--layout' is invalid");
         }
+        if (vm.count("rows")) {
+            if (vm["rows"] == "indices") c.GpuConfig.RowsAsIndices = true;
+            else if (vm["rows"] != "payloads")
+                throw std::invalid_argument("the argument ('" + vm["rows"] + "') for option '--rows' is invalid");
+        }
         c.GpuConfig.Hash = PHJ_HASH_XXH3;
         if (vm.count("hash")) {
             if (vm["hash"] == "xxh3" || vm["hash"] == "xxhash") c.GpuConfig.Hash = PHJ_HASH_XXH3;
@@ -253,6 +263,10 @@ Common::Configuration parseArguments(int argc, char** argv) {
             throw std::invalid_argument("--aggregate runs on one device");
         if (c.GpuConfig.Columns && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--layout columns runs on one device");
+        if (c.GpuConfig.RowsAsIndices && !c.GpuConfig.RowClasses && !c.GpuConfig.MaterializeAll)
+            throw std::invalid_argument("--rows indices makes the rows of --join-kind or --materialize all: give one of them");
+        if (c.GpuConfig.RowsAsIndices && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
+            throw std::invalid_argument("--rows indices runs on one device");
         // validateParsedConfiguration (src/Arguments.hpp:7-18)
         c.OutputConfig.Validate();
         c.OutputFormatConfig.Validate();
