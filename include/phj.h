@@ -546,6 +546,65 @@ const phj_group_row *phj_group_rows(phj_ctx *ctx, uint64_t *n);
 /* Copy the first n group rows of the last aggregate join to host memory. */
 int phj_group_download(phj_ctx *ctx, phj_group_row *host, uint64_t n);
 
+/* ---- membership (semi / anti join) as masks in the caller's row order ----
+ * Replaces nothing in the reference, which counts the probe tuples with a
+ * partner but does not say which they are. phj_join_member answers "which of
+ * my rows have a partner on the other side?" (SQL's IN / EXISTS, torch.isin):
+ * one byte per row, row i at byte i, so `cols[mask]` is the semi join and
+ * `cols[~mask]` the anti join of any number of columns.
+ *  - Masks. Each mask is a caller's DEVICE buffer of one byte per row of the
+ *    relation as bound (probe_mask: probe side, build_mask: build side), the
+ *    byte layout of a torch.bool tensor. Every byte in [0, n) is written as 0
+ *    or 1 and no byte outside that range is touched. The pointers need no
+ *    alignment: a slice of a tensor at an odd offset is valid.
+ *  - sides is a set of PHJ_MEMBER_PROBE / PHJ_MEMBER_BUILD. A mask whose side
+ *    is not asked may be NULL and is not touched; a side asked with a NULL
+ *    mask gives PHJ_ERR_INVALID unless that relation has 0 rows; sides == 0 or
+ *    a bit above 0x2 gives PHJ_ERR_INVALID.
+ *  - Synchronous, on the context's stream. r->matches == n->probe_matched ==
+ *    phj_join's matches for the same relations; n->build_matched is filled
+ *    when PHJ_MEMBER_BUILD is asked, else 0.
+ *  - Keys only, nothing packed: of a side bound as columns the key column is
+ *    read (the payload column is never touched, and a key column alone is
+ *    enough), of a side bound as tuples the ids (8 B at stride 16).
+ *    phj_relation_info.packed stays as it was and no `*.pack` timer appears.
+ *  - One schedule, whatever p asks for. p must pass the usual validation (a
+ *    known algo and hash; radix_bits / num_partitions in range for
+ *    PHJ_ALGO_RADIX) and p->hash / p->hash_seed are used, but algo, the radix
+ *    bits, num_partitions and table_ratio do not change what runs: R is
+ *    partitioned into region code tables (the NoPartitioning count's build)
+ *    and S is probed unpartitioned, in input order, so the answer for row i
+ *    comes out at lane i and the mask is a coalesced write. With
+ *    PHJ_MEMBER_BUILD every probe hit also marks the table slot it matched,
+ *    and a second pass over R in input order reads its key's mark.
+ *  - Single-device contexts only: a group or rank context returns
+ *    PHJ_ERR_STATE ("single-device contexts only").
+ *  - An empty side is not an error (unlike NoPartitioning's phj_join): the
+ *    other side's mask is all 0, the counts are 0, no join runs. The build
+ *    side is limited to 2^30 - 1 rows (PHJ_ERR_RANGE above).
+ *  - Nothing else is disturbed: the rows and index columns of earlier
+ *    materialised or index joins and the group rows stay as they are, and a
+ *    phj_join on the same context afterwards is exact (the code-table
+ *    workspace is shared, the marks are a buffer of their own that the call
+ *    clears before each join that asks for the build side).
+ *  - Timers: `R.p1.*` / `R.p2.scatter` and `np.build` as phj_join's
+ *    NoPartitioning count reports them (a key column is accounted 8 B per row
+ *    read where tuples are 16), `member.probe` (S's keys read, 8 B or 16 B per
+ *    row, the tables, the mask written) and, with PHJ_MEMBER_BUILD,
+ *    `member.build` (R's keys read again, a bucket and a mark per row, the
+ *    mask written). algorithmic_bytes follows these (DESIGN.md §3 "Membership
+ *    joins"). phj_prepare is not extended: the call grows what it needs
+ *    before its first launch. */
+#define PHJ_MEMBER_PROBE 0x1   /* probe_mask[i] = 1 iff probe row i's key equals some build key */
+#define PHJ_MEMBER_BUILD 0x2   /* build_mask[i] = 1 iff build row i's key equals some probe key */
+typedef struct phj_member_counts {   /* 16 B */
+    uint64_t probe_matched;   /* always filled == phj_join's matches for the same relations */
+    uint64_t build_matched;   /* filled when PHJ_MEMBER_BUILD is asked, else 0 */
+} phj_member_counts;
+int phj_join_member(phj_ctx *ctx, const phj_join_params *p, uint32_t sides,
+                    uint8_t *probe_mask, uint8_t *build_mask,
+                    phj_join_result *r, phj_member_counts *n);
+
 /* ---- building blocks (multi-GPU: range-sharded relations, RCCL exchange) ---- */
 /* Radix-partition the bound relation of `side`; fills `out` with ctx-owned views.
  * Asynchronous on the ctx stream (order later work on the same stream). */

@@ -18,7 +18,8 @@ from ._capi import (AGG_GROUPS, AGG_MATCHED_ONLY, ALGO_NO_PARTITIONING, ALGO_RAD
                     HASH_MURMUR3, HASH_XXH3, INNER, NULL_PAYLOAD, PATH_CODE_TABLES, PATH_LDS_JOIN,
                     PATH_NO_PARTITIONING, PATH_PARTITIONED, PROBE_ANTI, PROBE_OUTER, ROWS_BUILD_ONLY, ROWS_PAIRS,
                     ROWS_PROBE_ONLY, SIDE_BUILD, SIDE_PROBE, GroupRow, JoinParams, JoinResult, JoinTotals, Partitioned,
-                    PhjError, RowCounts, LAYOUT_TUPLES, LAYOUT_COLUMNS, RelationInfo, NO_ROW)
+                    PhjError, RowCounts, LAYOUT_TUPLES, LAYOUT_COLUMNS, RelationInfo, NO_ROW,
+                    MEMBER_PROBE, MEMBER_BUILD, MemberCounts)
 
 __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_JOIN", "PATH_CODE_TABLES",
            "PATH_PARTITIONED", "PATH_NO_PARTITIONING", "count_contribution", "count_verdict", "comm_unique_id", "CTX_EXCHANGE", "CTX_LOCAL", "radix_params", "nopart_params", "JoinParams", "JoinResult",
@@ -26,7 +27,8 @@ __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_J
            "HASH_MURMUR3", "SIDE_BUILD", "SIDE_PROBE", "DEFAULT_SEED", "RowCounts", "ROWS_PAIRS", "ROWS_PROBE_ONLY",
            "ROWS_BUILD_ONLY", "INNER", "PROBE_OUTER", "BUILD_OUTER", "FULL_OUTER", "PROBE_ANTI", "BUILD_ANTI",
            "NULL_PAYLOAD", "JoinTotals", "GroupRow", "AGG_GROUPS", "AGG_MATCHED_ONLY",
-           "RelationInfo", "LAYOUT_TUPLES", "LAYOUT_COLUMNS", "NO_ROW"]
+           "RelationInfo", "LAYOUT_TUPLES", "LAYOUT_COLUMNS", "NO_ROW",
+           "MEMBER_PROBE", "MEMBER_BUILD", "MemberCounts"]
 
 DEFAULT_SEED = 0x9E3779B97F4A7C15
 PART_STABLE = 0x1   # include/phj.h PHJ_PART_STABLE
@@ -402,6 +404,50 @@ class Context:
         r, t = JoinResult(), JoinTotals()
         self._check(self._L.phj_join_aggregate(self._h, C.byref(params), flags, C.byref(r), C.byref(t)))
         return r, t
+
+    def join_member(self, params: JoinParams, probe: bool = True, build: bool = False,
+                    probe_mask_ptr: int | None = None, build_mask_ptr: int | None = None):
+        """phj_join_member: which rows have a partner on the other side, one
+        byte per row in the relation's own order (probe: the probe side's mask,
+        build: the build side's). Only keys are read and nothing is packed; the
+        schedule is the same whatever `params` asks for beyond hash and seed.
+        Returns (JoinResult, MemberCounts, probe_mask, build_mask). A mask whose
+        device pointer is passed (any alignment, e.g. a torch.bool tensor's
+        data_ptr()) is written there and None is returned in its place;
+        otherwise the call allocates it on the device, downloads it and returns
+        a numpy bool array (None for a side that is not asked)."""
+        sides = (MEMBER_PROBE if probe else 0) | (MEMBER_BUILD if build else 0)
+        ptrs, own = [], []   # own[k]: None, or (scratch context holding the mask or None, rows) of a mask made here
+        r, cnt = JoinResult(), MemberCounts()
+        try:
+            for side, asked, ptr in ((SIDE_PROBE, probe, probe_mask_ptr), (SIDE_BUILD, build, build_mask_ptr)):
+                own.append(None)
+                if asked and ptr is None:
+                    n = self.relation_ptr(side)[1]
+                    donor = None
+                    if n:   # device memory for the mask: a scratch context's key column of ceil(n / 8) words
+                        donor = Context(self.device)
+                        own[-1] = (donor, n)
+                        donor.upload_columns(SIDE_PROBE, np.zeros((n + 7) // 8, dtype=np.int64))
+                        ptr = donor.columns_ptr(SIDE_PROBE)[0]
+                    own[-1] = (donor, n)
+                ptrs.append(ptr if asked else None)
+            self._check(self._L.phj_join_member(self._h, C.byref(params), sides, C.c_void_p(ptrs[0] or 0),
+                                                C.c_void_p(ptrs[1] or 0), C.byref(r), C.byref(cnt)))
+            masks = []
+            for o in own:
+                if o is None:
+                    masks.append(None)
+                elif o[0] is None:
+                    masks.append(np.zeros(0, dtype=bool))
+                else:
+                    words = np.ascontiguousarray(o[0].download(SIDE_PROBE)[:, 0])
+                    masks.append(words.view(np.uint8)[:o[1]].astype(bool))
+        finally:
+            for o in own:
+                if o is not None and o[0] is not None:
+                    o[0].close()
+        return r, cnt, masks[0], masks[1]
 
     def groups(self, n: int | None = None) -> np.ndarray:
         """Group rows of the last join_aggregate as an (n, 4) int64 array

@@ -45,6 +45,7 @@ EXPORTED = [
     "phj_relation_upload_columns", "phj_relation_bind_columns", "phj_relation_to_columns",
     "phj_relation_columns", "phj_relation_info_get",
     "phj_join_indices", "phj_joined_indices", "phj_joined_indices_download", "phj_gather_column",
+    "phj_join_member",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
@@ -58,6 +59,7 @@ NULL_PAYLOAD = -2**63   # the default marker for the missing side (INT64_MIN)
 AGG_GROUPS, AGG_MATCHED_ONLY = 0x1, 0x2   # phj_join_aggregate's flags
 LAYOUT_TUPLES, LAYOUT_COLUMNS = 0, 1   # phj_relation_info.layout
 NO_ROW = -1   # PHJ_NO_ROW: the missing side's row number in phj_join_indices' columns
+MEMBER_PROBE, MEMBER_BUILD = 0x1, 0x2   # phj_join_member's sides
 
 
 class Tuple(C.Structure):
@@ -111,6 +113,14 @@ class JoinTotals(C.Structure):
     def as_dict(self):
         return {"pairs": self.pairs, "probe_matched": self.probe_matched, "sum_a": self.sum_a,
                 "sum_b": self.sum_b, "sum_ab": self.sum_ab}
+
+
+class MemberCounts(C.Structure):
+    """phj_member_counts: rows with a partner, per side, of phj_join_member."""
+    _fields_ = [("probe_matched", C.c_uint64), ("build_matched", C.c_uint64)]
+
+    def as_dict(self):
+        return {"probe_matched": self.probe_matched, "build_matched": self.build_matched}
 
 
 class GroupRow(C.Structure):
@@ -217,6 +227,8 @@ def load():
         "phj_joined_indices": (i, [P, C.POINTER(P), C.POINTER(P), C.POINTER(u64)]),
         "phj_joined_indices_download": (i, [P, P, P, u64]),
         "phj_gather_column": (i, [P, P, u64, P, u64, C.POINTER(i64), P]),
+        "phj_join_member": (i, [P, C.POINTER(JoinParams), C.c_uint32, P, P, C.POINTER(JoinResult),
+                                C.POINTER(MemberCounts)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

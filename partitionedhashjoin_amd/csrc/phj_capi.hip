@@ -63,6 +63,7 @@
 #include "phj_partition.h"
 #include "phj_hot.h"
 #include "phj_table.h"
+#include "phj_member.h"
 
 using namespace phj;
 
@@ -204,6 +205,7 @@ struct phj_ctx {
     DevBuf np_tab, np_pays;
     DevBuf np_ovf, np_ovfb, np_ovfn;   // region build: overflow tuples, their start buckets, count
     DevBuf np_uni;                     // code-table NoPartitioning: {uniform?, cap} (k_np_ct_plan)
+    DevBuf member_marks;               // phj_join_member: one byte per slot of ht_tab (cleared before each join that marks)
     DevBuf fitems, split, cl_prof;
     DevBuf mat_mark, mat_cnt, mat_rows;   // materialised join: per-probe match, block offsets, rows
     DevBuf row_hit, row_only, row_cnt;    // phj_join_rows: build hit flags, probe-only bitmap, build block offsets
@@ -1566,11 +1568,14 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
 // bounds: one build segment of build_ht (they may point into an exchange block).
 // A cluster plan (pl.cluster, phj_cluster.h) stops after pass 1: `out` = the
 // codes contiguous per cluster, `bounds` = the nb1 + 1 cluster bounds.
-int partition_build(phj_ctx* c, const Plan& pl, int64_t* out, uint32_t* bounds) {
+// kcol (phj_join_member): a side bound as columns is read in place, pass 1
+// over its key column (8 B per tuple), whether or not a tuple copy exists.
+int partition_build(phj_ctx* c, const Plan& pl, int64_t* out, uint32_t* bounds, bool kcol = false) {
     SideState& S = c->side[PHJ_SIDE_BUILD];
     c->scan_scratch = &S.partials;
+    kcol = kcol && S.columns;
     if (!S.rel && !S.columns && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
-    if (!S.rel && !c->dry && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation bound as columns: no tuple copy was packed for this pass");
+    if (!kcol && !S.rel && !c->dry && S.n > 0) return set_err(c, PHJ_ERR_STATE, "relation bound as columns: no tuple copy was packed for this pass");
     if (S.n >= (1ull << 32) - 2 * 4096) return set_err(c, PHJ_ERR_RANGE, "relation above 2^32 tuples per device");
     constexpr int BLOCK = 512, ITEMS = 8, T = BLOCK * ITEMS;
     const uint32_t n = static_cast<uint32_t>(S.n), nb = pl.nb1, P = pl.Ppad;
@@ -1584,7 +1589,7 @@ int partition_build(phj_ctx* c, const Plan& pl, int64_t* out, uint32_t* bounds) 
         return PHJ_OK;
     }
     PassArgs a{};
-    a.in_keys = reinterpret_cast<const int64_t*>(S.rel);
+    a.in_keys = kcol ? S.ckeys : reinterpret_cast<const int64_t*>(S.rel);
     a.out_keys = pl.cluster ? out : static_cast<int64_t*>(S.kA.p);
     a.hist = static_cast<uint32_t*>(S.hist1.p);
     a.nseg = 1;
@@ -1596,20 +1601,22 @@ int partition_build(phj_ctx* c, const Plan& pl, int64_t* out, uint32_t* bounds) 
     a.xcd_remap = 1;
     const uint32_t grid = (nt + 7) & ~7u;
     const size_t hlds = static_cast<size_t>(BLOCK / 64) * nb * 4;
-    PHJ_TRY(timer_begin(c, "R.p1.hist", static_cast<uint64_t>(n) * 16));
+    PHJ_TRY(timer_begin(c, "R.p1.hist", static_cast<uint64_t>(n) * (kcol ? 8 : 16)));
     with_hash(pl.hk, [&](auto h) {
-        hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, true, decltype(h)::value>), dim3(grid), dim3(BLOCK), hlds, c->ks, a);
+        if (kcol) hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, false, decltype(h)::value, true>), dim3(grid), dim3(BLOCK), hlds, c->ks, a);
+        else hipLaunchKernelGGL((k_hist<BLOCK, ITEMS, true, decltype(h)::value>), dim3(grid), dim3(BLOCK), hlds, c->ks, a);
     });
     PHJ_LAUNCHED(c, "k_hist");
     PHJ_TRY(timer_end(c));
     PHJ_TRY(timer_begin(c, "R.p1.scan", static_cast<uint64_t>(hlen) * 12));
     PHJ_TRY(scan_u32(c, a.hist, hlen, 1, hlen, c->scan_scratch));   // k_ht_p2 reads d1's run from it
     PHJ_TRY(timer_end(c));
-    // algorithmic bytes: the 16-B tuple read, the 8-B code written
-    PHJ_TRY(timer_begin(c, "R.p1.scatter", static_cast<uint64_t>(n) * 24));
+    // algorithmic bytes: the 16-B tuple (or 8-B key) read, the 8-B code written
+    PHJ_TRY(timer_begin(c, "R.p1.scatter", static_cast<uint64_t>(n) * (kcol ? 16 : 24)));
     const size_t slds = scatter_codes_lds_bytes(T, nb);
     with_hash(pl.hk, [&](auto h) {
-        hipLaunchKernelGGL((k_scatter_codes<BLOCK, ITEMS, decltype(h)::value>), dim3(grid), dim3(BLOCK), slds, c->ks, a);
+        if (kcol) hipLaunchKernelGGL((k_scatter_codes<BLOCK, ITEMS, decltype(h)::value, true>), dim3(grid), dim3(BLOCK), slds, c->ks, a);
+        else hipLaunchKernelGGL((k_scatter_codes<BLOCK, ITEMS, decltype(h)::value>), dim3(grid), dim3(BLOCK), slds, c->ks, a);
     });
     PHJ_LAUNCHED(c, "k_scatter_codes");
     PHJ_TRY(timer_end(c));
@@ -2053,6 +2060,162 @@ int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     r->total_ms = elapsed(c, e0, e2);
     r->num_partitions = 0;
     r->algorithmic_bytes = R.n * (16 + 8 + 8 + 8) + R.n * 24 + S.n * 16 + R.n * 16;
+    return fill_timers(c, r);
+}
+
+// phj_join_member (phj_member.h): the build half of join_nopart_ct over keys
+// alone, then the membership probe (mask, count and, with the build side
+// asked, slot marks) and the pass over R that reads the marks.
+int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* probe_mask, uint8_t* build_mask,
+                phj_join_result* r, phj_member_counts* n) {
+    const char* what = "phj_join_member";
+    if (!c || !r || !n) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    (void)hipGetLastError();
+    if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
+    if (sides == 0 || (sides & ~static_cast<uint32_t>(PHJ_MEMBER_PROBE | PHJ_MEMBER_BUILD)))
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": sides must be a set of PHJ_MEMBER_PROBE / PHJ_MEMBER_BUILD");
+    if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
+        return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3) return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
+    if (p->algo == PHJ_ALGO_RADIX) {   // the usual validation; the plan itself is not used
+        Plan asked;
+        PHJ_TRY(make_plan(c, p, asked));
+    }
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    const bool want_s = (sides & PHJ_MEMBER_PROBE) != 0, want_b = (sides & PHJ_MEMBER_BUILD) != 0;
+    if ((want_s && !probe_mask && S.n > 0) || (want_b && !build_mask && R.n > 0))
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": a side that is asked needs its mask");
+    for (const SideState* X : {&R, &S})
+        if (!X->rel && !X->columns && X->n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    if (R.n >= (1ull << 30)) return set_err(c, PHJ_ERR_RANGE, std::string(what) + ": build side of 2^30 rows or more");
+    PHJ_HIP(c, hipSetDevice(c->device));
+    std::memset(r, 0, sizeof(*r));
+    std::memset(n, 0, sizeof(*n));
+    c->defer_timers = false;
+    c->lean_timers = false;
+    c->timer_skipped = false;
+    c->count_pinned = false;
+    c->ks = c->stream;
+    reset_timers(c);
+    // an empty side joins to nothing: the other side's mask is all 0, no join runs
+    if (R.n == 0 || S.n == 0) {
+        if (want_s && S.n > 0) PHJ_HIP(c, hipMemsetAsync(probe_mask, 0, S.n, c->ks));
+        if (want_b && R.n > 0) PHJ_HIP(c, hipMemsetAsync(build_mask, 0, R.n, c->ks));
+        PHJ_HIP(c, hipStreamSynchronize(c->ks));
+        return PHJ_OK;
+    }
+    // keys alone: a side bound as columns is read from its key column, packed or not
+    const bool r_keys = R.columns, s_keys = S.columns;
+    const uint64_t rk = r_keys ? 8 : 16, sk = s_keys ? 8 : 16;
+    uint32_t k = 2;
+    while (k < 22 && (R.n >> k) > 300) k++;
+    phj_join_params pp = *p;
+    pp.algo = PHJ_ALGO_RADIX;
+    pp.num_partitions = 0;
+    pp.flags = 0;
+    pp.radix_bits[1] = static_cast<uint8_t>(k / 2);
+    pp.radix_bits[0] = static_cast<uint8_t>(k - k / 2);
+    Plan pl;
+    PHJ_TRY(make_plan(c, &pp, pl));
+    const uint32_t P = pl.Ppad;
+    const uint64_t slot_bound = 4 * R.n + 2ull * P;
+    PHJ_TRY(ensure(c, c->r_codes, R.n * 8));
+    PHJ_TRY(ensure(c, c->r_bounds, (static_cast<size_t>(P) + 1) * 4));
+    PHJ_TRY(ensure(c, c->np_uni, 16));
+    PHJ_TRY(ensure(c, c->count, 32));
+    if (want_b) PHJ_TRY(ensure(c, c->member_marks, slot_bound));
+    const int64_t* rcodes = static_cast<const int64_t*>(c->r_codes.p);
+    const uint32_t* rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
+    auto* uni = static_cast<uint32_t*>(c->np_uni.p);
+    auto* cnt = static_cast<unsigned long long*>(c->count.p);
+    hipEvent_t e0, e1, e2;
+    PHJ_TRY(mark(c, &e0));
+    PHJ_TRY(partition_build(c, pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p), r_keys));
+    PHJ_TRY(timer_begin(c, "np.build", R.n * 8 * 3));
+    hipLaunchKernelGGL(k_np_ct_plan, dim3(1), dim3(256), 0, c->ks, rbnd, P, slot_bound, uni);
+    PHJ_LAUNCHED(c, "k_np_ct_plan");
+    PHJ_TRY(build_ht(c, pl, 1, &rcodes, &rbnd, R.n, uni));
+    PHJ_TRY(timer_end(c));
+    PHJ_TRY(mark(c, &e1));
+    PHJ_HIP(c, hipMemsetAsync(cnt, 0, 32, c->ks));
+    const uint64_t per = 256ull * kMemberItems;
+    {
+        // algorithmic bytes: S's keys read once, R's tables (~2 slots per code) once, the mask
+        // written; with marks the slot bytes cleared and (at most) one stored per hit's line
+        PHJ_TRY(timer_begin(c, "member.probe", S.n * sk + R.n * 16 + (want_s ? S.n : 0) + (want_b ? slot_bound : 0)));
+        if (want_b) PHJ_HIP(c, hipMemsetAsync(c->member_marks.p, 0, slot_bound, c->ks));
+        const void* kfn = with_hash(p->hash, [&](auto h) {
+            constexpr int HK = decltype(h)::value;
+            auto pick = [&](auto KEYS, auto MARK) {
+                constexpr bool K = decltype(KEYS)::value, M = decltype(MARK)::value;
+                return reinterpret_cast<const void*>(&k_np_member_probe<HK, kMemberItems, K, M>);
+            };
+            return s_keys ? (want_b ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{}))
+                          : (want_b ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{}));
+        });
+        int per_cu = 0;
+        if ((per_cu = occupancy(kfn, 256, 0)) < 1) per_cu = 8;
+        const uint64_t want = (S.n + per - 1) / per;
+        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want, static_cast<uint64_t>(per_cu) * c->num_cus)));
+        MemberProbeArgs a{};
+        a.keys = s_keys ? S.ckeys : reinterpret_cast<const int64_t*>(S.rel);
+        a.n = S.n;
+        a.table = static_cast<const uint64_t*>(c->ht_tab.p);
+        a.desc = static_cast<const uint2*>(c->ht_desc.p);
+        a.uni = uni;
+        a.P = P;
+        a.seed = p->hash_seed;
+        a.e1 = plan_empty0(pl);
+        a.mask = want_s ? probe_mask : nullptr;
+        a.marks = want_b ? static_cast<uint8_t*>(c->member_marks.p) : nullptr;
+        a.count = cnt;
+        void* kargs[] = {&a};
+        PHJ_TRY(launch_kernel(c, kfn, dim3(grid), dim3(256), kargs, 0, "k_np_member_probe"));
+        PHJ_TRY(timer_end(c));
+    }
+    if (want_b) {
+        // algorithmic bytes: R's keys read again, a bucket and a mark per row, the mask written
+        PHJ_TRY(timer_begin(c, "member.build", R.n * (rk + 16 + 1 + 1)));
+        const void* kfn = with_hash(p->hash, [&](auto h) {
+            constexpr int HK = decltype(h)::value;
+            return r_keys ? reinterpret_cast<const void*>(&k_member_build<HK, true>)
+                          : reinterpret_cast<const void*>(&k_member_build<HK, false>);
+        });
+        const uint64_t want = (R.n + per - 1) / per;
+        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want, 8ull * c->num_cus)));
+        MemberBuildArgs a{};
+        a.keys = r_keys ? R.ckeys : reinterpret_cast<const int64_t*>(R.rel);
+        a.n = R.n;
+        a.table = static_cast<const uint64_t*>(c->ht_tab.p);
+        a.desc = static_cast<const uint2*>(c->ht_desc.p);
+        a.uni = uni;
+        a.P = P;
+        a.seed = p->hash_seed;
+        a.e1 = plan_empty0(pl);
+        a.mask = build_mask;
+        a.marks = static_cast<const uint8_t*>(c->member_marks.p);
+        a.count = cnt + 1;
+        void* kargs[] = {&a};
+        PHJ_TRY(launch_kernel(c, kfn, dim3(grid), dim3(256), kargs, 0, "k_member_build"));
+        PHJ_TRY(timer_end(c));
+    }
+    PHJ_TRY(mark(c, &e2));
+    unsigned long long h[3] = {0, 0, 0};   // {probe rows matched, build rows matched, a build key was not found}
+    PHJ_HIP(c, hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->ks));
+    PHJ_HIP(c, hipStreamSynchronize(c->ks));
+    if (h[2]) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": a build key was not found in its region's table");
+    n->probe_matched = h[0];
+    n->build_matched = want_b ? h[1] : 0;
+    r->matches = h[0];
+    r->partition_ms = 0;
+    r->build_ms = elapsed(c, e0, e1);
+    r->probe_ms = elapsed(c, e1, e2);
+    r->total_ms = elapsed(c, e0, e2);
+    r->num_partitions = 0;
+    r->algorithmic_bytes = R.n * (rk + (rk + 8) + 16) + R.n * 24 + S.n * sk + R.n * 16 + (want_s ? S.n : 0) +
+                           (want_b ? slot_bound + R.n * (rk + 16 + 1 + 1) : 0);
     return fill_timers(c, r);
 }
 
@@ -3315,7 +3478,7 @@ void phj_ctx_destroy(phj_ctx* c) {
             free_buf(*b);
     }
     for (DevBuf* b : {&c->ht_tab, &c->ht_desc, &c->r_codes, &c->r_bounds, &c->scan_partials, &c->prep, &c->tkeys, &c->tpays, &c->toffs, &c->gcursor, &c->items, &c->biglist,
-                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->agg_acc, &c->agg_cnt, &c->agg_rows, &c->agg_res, &c->cl_done, &c->hot, &c->gather_bad})
+                      &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->agg_acc, &c->agg_cnt, &c->agg_rows, &c->agg_res, &c->cl_done, &c->hot, &c->gather_bad, &c->member_marks})
         free_buf(*b);
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     for (hipEvent_t e : {c->hot_fork, c->hot_join})
@@ -4210,6 +4373,14 @@ int phj_group_download(phj_ctx* c, phj_group_row* host, uint64_t n) {
     PHJ_HIP(c, hipMemcpyAsync(host, c->agg_rows.p, n * sizeof(phj_group_row), hipMemcpyDeviceToHost, c->stream));
     PHJ_HIP(c, hipStreamSynchronize(c->stream));
     return PHJ_OK;
+}
+
+// ---- membership joins (phj_member.h) ----
+static_assert(sizeof(phj_member_counts) == 16, "phj_member_counts layout");
+
+int phj_join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* probe_mask, uint8_t* build_mask,
+                    phj_join_result* r, phj_member_counts* n) {
+    return join_member(c, p, sides, probe_mask, build_mask, r, n);
 }
 
 int phj_probe_pass1(phj_ctx* c, const phj_join_params* p, int64_t* keys, uint64_t n, uint32_t* bounds1,

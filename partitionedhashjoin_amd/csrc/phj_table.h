@@ -88,12 +88,14 @@ __device__ __forceinline__ uint32_t agg_rank(uint32_t* C, uint32_t d, bool valid
 // by one LDS atomic per key (the order inside a partition is free), sorted by
 // digit in LDS and written so consecutive lanes fill consecutive slots of each
 // digit run. Offsets from k_hist's scanned histogram (hist[d * ntiles + t]).
+// KCOL (phj_member.h, a side bound as columns): the relation is a key column,
+// 8 B per tuple read in place.
 // ---------------------------------------------------------------------------
 __host__ __device__ constexpr size_t scatter_codes_lds_bytes(int T, uint32_t nb) {
     return static_cast<size_t>(T) * (8 + (nb <= 256 ? 1 : 2)) + static_cast<size_t>(nb) * 12 + 64 + 16;
 }
 
-template <int BLOCK, int ITEMS, int HK>
+template <int BLOCK, int ITEMS, int HK, bool KCOL = false>
 __global__ __launch_bounds__(BLOCK) void k_scatter_codes(PassArgs a) {
     __builtin_amdgcn_s_setprio(3);   // R's chain: issue ahead of the persistent S pass 1 sharing the SIMD
     constexpr int T = BLOCK * ITEMS;
@@ -120,7 +122,8 @@ __global__ __launch_bounds__(BLOCK) void k_scatter_codes(PassArgs a) {
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const uint32_t e = wbase + i * 64 + lane;
-        code[i] = e < n ? rel[L.lo + e].x : 0;
+        if constexpr (KCOL) code[i] = e < n ? a.in_keys[L.lo + e] : 0;
+        else code[i] = e < n ? rel[L.lo + e].x : 0;
     }
     __syncthreads();
 #pragma unroll

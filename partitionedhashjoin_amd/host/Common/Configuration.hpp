@@ -76,6 +76,7 @@ struct GpuConfiguration {
     int64_t NullPayload = INT64_MIN; // ... the payload standing for the missing side of an outer / anti row
     bool RowsAsIndices = false;      // --rows indices: the rows come from phj_join_indices on the key columns alone, composed with phj_gather_column
     int Aggregate = 0;               // --aggregate totals | groups: 1 / 2, Run() reports the join's aggregates (phj_join_aggregate; 0 = off)
+    uint32_t Member = 0;             // --member probe | build | both: Run() reports which rows have a partner (phj_join_member; PHJ_MEMBER_* set, 0 = off)
     bool Columns = false;            // --layout columns: both relations are split into key / payload columns on the device before the join (phj_relation_to_columns)
     std::vector<int> Devices;       // --gpus N / --devices a,b,..: the context's devices (empty: {Device})
     uint32_t ContextFlags = 0;       // --exchange rccl|local: PHJ_CTX_EXCHANGE / PHJ_CTX_LOCAL

@@ -24,6 +24,11 @@
 // (phj_join_aggregate: `pairs`, `probe_matched`, `sum_a`, `sum_b`, `sum_ab`
 // added to the results; for groups also `groups` and `groups_checksum` over
 // the group rows copied back); the returned table is empty, matches = pairs.
+// GpuConfiguration::Member asks which rows have a partner on the other side
+// (phj_join_member into masks held by a scratch context, copied back):
+// `probe_matched`, `build_matched` and, per asked side, `probe_mask_checksum`
+// / `build_mask_checksum` = Σ (i + 1) · mask[i] mod 2^64 are added to the
+// results; the returned table is empty, matches = probe_matched.
 // GpuConfiguration::Columns binds both relations as key / payload columns
 // (phj_relation_to_columns) before whatever was asked for runs; the results'
 // `layout` says which binding ran.
@@ -157,6 +162,42 @@ inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join_by_indices(Devic
     return out;
 }
 
+// --member: the masks of phj_join_member. The C ABI has no allocator: a mask
+// is the key column of a scratch context's relation on the same device
+// (ceil(n / 8) words), read back as tuples.
+inline void join_member(Device& dev, const phj_join_params& p, phj_join_result& r, uint32_t sides,
+                        Common::IHashJoinTimer& timer) {
+    phj_ctx* c = dev.Get();
+    Device scratch(dev.DeviceId());
+    uint64_t n[2] = {0, 0};
+    uint8_t* mask[2] = {nullptr, nullptr};
+    const uint32_t bit[2] = {PHJ_MEMBER_BUILD, PHJ_MEMBER_PROBE};   // indexed by PHJ_SIDE_BUILD / PHJ_SIDE_PROBE
+    for (int side : {PHJ_SIDE_BUILD, PHJ_SIDE_PROBE}) {
+        (void)phj_relation_device_ptr(c, side, &n[side]);
+        if (!(sides & bit[side]) || n[side] == 0) continue;
+        const std::vector<int64_t> zeros((n[side] + 7) / 8, 0);
+        scratch.Check(phj_relation_upload_columns(scratch.Get(), side, zeros.data(), nullptr, zeros.size()));
+        const int64_t* col = nullptr;
+        scratch.Check(phj_relation_columns(scratch.Get(), side, &col, nullptr, nullptr));
+        mask[side] = reinterpret_cast<uint8_t*>(const_cast<int64_t*>(col));
+    }
+    phj_member_counts m{};
+    dev.Check(phj_join_member(c, &p, sides, mask[PHJ_SIDE_PROBE], mask[PHJ_SIDE_BUILD], &r, &m));
+    timer.AddResult("probe_matched", std::to_string(m.probe_matched));
+    timer.AddResult("build_matched", std::to_string(m.build_matched));
+    for (int side : {PHJ_SIDE_PROBE, PHJ_SIDE_BUILD}) {
+        if (!(sides & bit[side])) continue;
+        uint64_t sum = 0;
+        if (mask[side]) {
+            std::vector<phj_tuple> t((n[side] + 7) / 8);
+            scratch.Check(phj_relation_download(scratch.Get(), side, t.data(), t.size()));
+            for (uint64_t i = 0; i < n[side]; i++)
+                sum += (i + 1) * ((static_cast<uint64_t>(t[i / 8].id) >> (8 * (i % 8))) & 0xffu);
+        }
+        timer.AddResult(side == PHJ_SIDE_PROBE ? "probe_mask_checksum" : "build_mask_checksum", std::to_string(sum));
+    }
+}
+
 // phj_join or, with rows requested, phj_join_materialize (one row per matching
 // probe tuple) / phj_join_inner (all: one row per pair) + the rows copied into
 // the returned table; with gpu.RowClasses, phj_join_rows of that kind
@@ -165,6 +206,10 @@ inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, con
                                                                 const Common::GpuConfiguration& gpu,
                                                                 Common::IHashJoinTimer& timer) {
     const bool materialize = gpu.Materialize, all = gpu.MaterializeAll;
+    if (gpu.Member != 0) {
+        join_member(dev, p, r, gpu.Member, timer);
+        return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());
+    }
     if (gpu.Aggregate != 0) {
         phj_join_totals t{};
         dev.Check(phj_join_aggregate(dev.Get(), &p, gpu.Aggregate == 2 ? PHJ_AGG_GROUPS : 0u, &r, &t));

@@ -20,6 +20,7 @@
 //   --aggregate A         totals|groups: report the join's aggregates instead of rows
 //   --layout L            tuples|columns: bind the relations as {id, payload} tuples or as key / payload columns
 //   --rows W              payloads|indices: how the returned rows are made (indices: an index join on the key columns, then gathers)
+//   --member M            probe|build|both: report which rows have a partner on the other side (counts and mask checksums)
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -84,6 +85,11 @@ const char* kHelp =
     "                                      indices: both relations are split into columns, only the key columns\n"
     "                                      stay bound, phj_join_indices returns (build row, probe row) pairs and\n"
     "                                      phj_gather_column composes the rows from them. One device only.\n"
+    "  --member arg                        probe | build | both: which rows of that side have a partner on the other\n"
+    "                                      (phj_join_member: one byte per row in input order, only keys are read):\n"
+    "                                      probe_matched, build_matched and, per asked side, a checksum of its mask,\n"
+    "                                      sum of (i + 1) * mask[i] modulo 2^64. One device only, and not together\n"
+    "                                      with returned rows or aggregates.\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
@@ -118,7 +124,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
     static const std::set<std::string> known = {"help", "primary", "secondary", "skew", "log", "join", "format",
                                                 "unit", "output", "filename", "partitions", "device", "gpus", "devices", "exchange", "hash",
                                                 "radix-bits", "seed", "hash-seed", "generate", "table-ratio",
-                                                "materialize", "join-kind", "aggregate", "layout", "rows"};
+                                                "materialize", "join-kind", "aggregate", "layout", "rows", "member"};
     Common::Configuration c{};
     c.OutputFormatConfig.TimeUnit = "ms";
     c.OutputConfig.File.Name = "hashjoin.txt";
@@ -199,6 +205,12 @@ Common::Configuration parseArguments(int argc, char** argv) {
             else if (vm["rows"] != "payloads")
                 throw std::invalid_argument("the argument ('" + vm["rows"] + "') for option '--rows' is invalid");
         }
+        if (vm.count("member")) {
+            if (vm["member"] == "probe") c.GpuConfig.Member = PHJ_MEMBER_PROBE;
+            else if (vm["member"] == "build") c.GpuConfig.Member = PHJ_MEMBER_BUILD;
+            else if (vm["member"] == "both") c.GpuConfig.Member = PHJ_MEMBER_PROBE | PHJ_MEMBER_BUILD;
+            else throw std::invalid_argument("the argument ('" + vm["member"] + "') for option '--member' is invalid");
+        }
         c.GpuConfig.Hash = PHJ_HASH_XXH3;
         if (vm.count("hash")) {
             if (vm["hash"] == "xxh3" || vm["hash"] == "xxhash") c.GpuConfig.Hash = PHJ_HASH_XXH3;
@@ -261,6 +273,12 @@ Common::Configuration parseArguments(int argc, char** argv) {
             throw std::invalid_argument("--aggregate returns no rows: not together with --materialize on / all or --join-kind");
         if (c.GpuConfig.Aggregate && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--aggregate runs on one device");
+        if (c.GpuConfig.Member && (c.GpuConfig.Materialize || c.GpuConfig.MaterializeAll || c.GpuConfig.RowClasses ||
+                                   c.GpuConfig.Aggregate || vm.count("rows")))
+            throw std::invalid_argument(
+                "--member returns no rows: not together with --materialize on / all, --join-kind, --aggregate or --rows");
+        if (c.GpuConfig.Member && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
+            throw std::invalid_argument("--member runs on one device");
         if (c.GpuConfig.Columns && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--layout columns runs on one device");
         if (c.GpuConfig.RowsAsIndices && !c.GpuConfig.RowClasses && !c.GpuConfig.MaterializeAll)
