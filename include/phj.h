@@ -605,6 +605,78 @@ int phj_join_member(phj_ctx *ctx, const phj_join_params *p, uint32_t sides,
                     uint8_t *probe_mask, uint8_t *build_mask,
                     phj_join_result *r, phj_member_counts *n);
 
+/* ---- a retained key index: build once, look up key batches in-stream ----
+ * Replaces nothing in the reference, whose tables live for one Run(). Every
+ * join above takes both relations and rebuilds R's tables per call; a caller
+ * with one dimension or dictionary table and a stream of key batches wants
+ * "key -> row of the table" per batch, on its own stream, with nothing coming
+ * back to the host (pandas.Index.get_indexer, an embedding-id lookup, a
+ * foreign-key resolve). phj_index_build makes the table once and keeps it;
+ * phj_index_lookup is one kernel launch.
+ *
+ * phj_index_build indexes the build side as bound (tuples, columns, or a key
+ * column alone). It reads keys only and packs nothing: phj_relation_info.packed
+ * stays as it was and no `*.pack` timer appears.
+ *  - Entries: each distinct key once, with the lowest build row that carries
+ *    it (its first occurrence). A key repeated a million times is one entry
+ *    and lengthens no lookup's walk.
+ *  - Synchronous; fills r: r->matches = the distinct key count; timers
+ *    `R.p1.*` / `R.p2.scatter` as the NoPartitioning joins report them and
+ *    `index.build` (the partitioned keys and rows read, 16 B per row, and every
+ *    bucket written); algorithmic_bytes is the sum of the timers' bytes.
+ *  - p passes the usual validation; p->hash, p->hash_seed and p->table_ratio
+ *    (slots per build row, >= 1; 0 selects the default 2.0) are used; algo and
+ *    the radix fields do not change what runs (phj_join_member's rule).
+ *  - Geometry (phj_index_info) depends on the row count and table_ratio alone:
+ *    nb buckets of `slots` = 5 entries in 2^rbits regions of nbr buckets,
+ *    1 <= rbits <= 22. A key's region is the low rbits of its hash code, its
+ *    home bucket inside the region (high word of the code * nbr) >> 32; the
+ *    walk goes bucket by bucket over the whole table and wraps at its end. A
+ *    bucket is one 64-byte line holding five codes, their five rows and a fill
+ *    count, so a lookup that settles at home reads one line. Liveness is the
+ *    fill count: no key value is reserved (0, -1, INT64_MIN, INT64_MAX are
+ *    keys like any other).
+ *  - The index owns its memory (phj_index_info.table_bytes) and stays valid
+ *    until phj_index_destroy or phj_ctx_destroy, which frees survivors. No
+ *    later join on the context, no rebinding of either side and no freeing of
+ *    a borrowed key column disturbs it. Several indexes may coexist.
+ *  - An empty build side gives a valid index over which every lookup misses.
+ *    The build side is limited to 2^30 - 1 rows (PHJ_ERR_RANGE above, before
+ *    any launch). Single-device contexts only: a group or rank context returns
+ *    PHJ_ERR_STATE ("single-device contexts only").
+ *
+ * phj_index_lookup enqueues one kernel on the context's stream
+ * (phj_ctx_set_stream, or the context's own) and returns at once: it does not
+ * synchronise, read anything back, record events or timers, or allocate.
+ *  - dev_keys: any device address, 8-byte aligned, not a bound relation; key i
+ *    is dev_keys[i * key_stride], key_stride 1 (a key column) or 2 (the ids of
+ *    a tuple array); anything else gives PHJ_ERR_INVALID.
+ *  - out_rows[i] = the lowest build row whose key equals key i, or PHJ_NO_ROW:
+ *    an index column for phj_gather_column or torch's index_select. 8-byte
+ *    aligned, required unless n == 0.
+ *  - out_found (optional): one byte per key, 0 or 1, at any alignment (a
+ *    torch.bool tensor or an odd-offset slice of one).
+ *  - dev_found_count (optional, 8-byte aligned): a device counter to which the
+ *    number of found keys is added; the caller zeroes it.
+ *  - Exactly [0, n) of each output is written. n == 0 is PHJ_OK and launches
+ *    nothing.
+ *  - The index must belong to ctx. Lookups of one context run in stream order;
+ *    phj_ctx_synchronize (or the caller's own stream) waits for them. */
+typedef struct phj_index phj_index;
+typedef struct phj_index_info {   /* 40 B */
+    uint64_t rows;        /* build rows indexed */
+    uint64_t distinct;    /* distinct keys among them == entries of the table */
+    uint64_t table_bytes; /* device memory the index holds */
+    uint32_t nb, nbr, rbits, slots;  /* geometry: buckets, buckets per region, region bits, key slots per bucket */
+} phj_index_info;
+int phj_index_build(phj_ctx *ctx, const phj_join_params *p, phj_index **out, phj_join_result *r);
+int phj_index_info_get(const phj_index *index, phj_index_info *out);
+int phj_index_lookup(phj_ctx *ctx, const phj_index *index, const int64_t *dev_keys, uint32_t key_stride, uint64_t n,
+                     int64_t *out_rows, uint8_t *out_found, unsigned long long *dev_found_count);
+/* Frees the index (after the lookups already in the stream). An index that
+ * ctx does not hold (destroyed before, or another context's) is ignored. */
+void phj_index_destroy(phj_ctx *ctx, phj_index *index);
+
 /* ---- building blocks (multi-GPU: range-sharded relations, RCCL exchange) ---- */
 /* Radix-partition the bound relation of `side`; fills `out` with ctx-owned views.
  * Asynchronous on the ctx stream (order later work on the same stream). */

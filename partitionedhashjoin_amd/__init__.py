@@ -19,7 +19,7 @@ from ._capi import (AGG_GROUPS, AGG_MATCHED_ONLY, ALGO_NO_PARTITIONING, ALGO_RAD
                     PATH_NO_PARTITIONING, PATH_PARTITIONED, PROBE_ANTI, PROBE_OUTER, ROWS_BUILD_ONLY, ROWS_PAIRS,
                     ROWS_PROBE_ONLY, SIDE_BUILD, SIDE_PROBE, GroupRow, JoinParams, JoinResult, JoinTotals, Partitioned,
                     PhjError, RowCounts, LAYOUT_TUPLES, LAYOUT_COLUMNS, RelationInfo, NO_ROW,
-                    MEMBER_PROBE, MEMBER_BUILD, MemberCounts)
+                    MEMBER_PROBE, MEMBER_BUILD, MemberCounts, IndexInfo)
 
 __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_JOIN", "PATH_CODE_TABLES",
            "PATH_PARTITIONED", "PATH_NO_PARTITIONING", "count_contribution", "count_verdict", "comm_unique_id", "CTX_EXCHANGE", "CTX_LOCAL", "radix_params", "nopart_params", "JoinParams", "JoinResult",
@@ -28,7 +28,7 @@ __all__ = ["Context", "shard_range", "exchange_layout", "join_path", "PATH_LDS_J
            "ROWS_BUILD_ONLY", "INNER", "PROBE_OUTER", "BUILD_OUTER", "FULL_OUTER", "PROBE_ANTI", "BUILD_ANTI",
            "NULL_PAYLOAD", "JoinTotals", "GroupRow", "AGG_GROUPS", "AGG_MATCHED_ONLY",
            "RelationInfo", "LAYOUT_TUPLES", "LAYOUT_COLUMNS", "NO_ROW",
-           "MEMBER_PROBE", "MEMBER_BUILD", "MemberCounts"]
+           "MEMBER_PROBE", "MEMBER_BUILD", "MemberCounts", "Index", "IndexInfo"]
 
 DEFAULT_SEED = 0x9E3779B97F4A7C15
 PART_STABLE = 0x1   # include/phj.h PHJ_PART_STABLE
@@ -187,6 +187,9 @@ class Context:
     # -- lifecycle --
     def close(self):
         if getattr(self, "_h", None):
+            for ix in getattr(self, "_indexes", []):   # phj_ctx_destroy frees the survivors
+                ix._h = None
+            self._indexes = []
             self._L.phj_ctx_destroy(self._h)
             self._h = None
 
@@ -449,6 +452,21 @@ class Context:
                     o[0].close()
         return r, cnt, masks[0], masks[1]
 
+    def build_index(self, params: JoinParams) -> "Index":
+        """phj_index_build: a retained key index over the build side as bound
+        (keys only; any binding, a key column alone included): each distinct
+        key once with the lowest row that carries it. The index owns its
+        memory and outlives later joins and rebinds of this context; close it
+        with Index.close() (closing the context closes its indexes). The
+        build's JoinResult is Index.result (matches = the distinct keys)."""
+        h, r = C.c_void_p(), JoinResult()
+        self._check(self._L.phj_index_build(self._h, C.byref(params), C.byref(h), C.byref(r)))
+        ix = Index(self, h, r)
+        if not hasattr(self, "_indexes"):
+            self._indexes = []
+        self._indexes.append(ix)
+        return ix
+
     def groups(self, n: int | None = None) -> np.ndarray:
         """Group rows of the last join_aggregate as an (n, 4) int64 array
         {id, payloadA, partners, sum of the partners' payloads}, in unspecified
@@ -542,3 +560,72 @@ class Context:
         self._check(self._L.phj_hash_keys(self._h, kind, seed, keys.ctypes.data_as(C.c_void_p),
                                           keys.shape[0], out.ctypes.data_as(C.c_void_p)))
         return out
+
+
+class Index:
+    """A phj_index: a retained key index of one Context (Context.build_index).
+    lookup() is enqueue-only on the context's stream; lookup_host() is the
+    numpy convenience around it."""
+
+    def __init__(self, ctx: Context, handle, result: JoinResult):
+        self._ctx, self._h, self.result = ctx, handle, result
+
+    def _handle(self):
+        if not self._h or not self._ctx._h:
+            raise PhjError(_capi.PHJ_ERR_STATE, "the index is closed")
+        return self._h
+
+    def info(self) -> IndexInfo:
+        out = IndexInfo()
+        rc = self._ctx._L.phj_index_info_get(self._handle(), C.byref(out))
+        if rc != 0:
+            raise PhjError(rc, "phj_index_info_get failed")
+        return out
+
+    def lookup(self, keys_ptr: int, n: int, rows_ptr: int, found_ptr: int | None = None,
+               count_ptr: int | None = None, key_stride: int = 1) -> None:
+        """phj_index_lookup on device pointers, enqueued on the context's stream
+        (nothing is synchronised or read back): rows[i] = the lowest build row
+        whose key equals keys[i * key_stride], or NO_ROW; found[i] (optional,
+        one byte per key, any alignment) = 0 / 1; the number of found keys is
+        added to the uint64 at count_ptr (optional; the caller zeroes it)."""
+        c = self._ctx
+        c._check(c._L.phj_index_lookup(c._h, self._handle(), C.c_void_p(keys_ptr or 0), key_stride, n,
+                                       C.c_void_p(rows_ptr or 0), C.c_void_p(found_ptr or 0),
+                                       C.c_void_p(count_ptr or 0)))
+
+    def lookup_host(self, keys):
+        """(rows, found) for a host array of int64 keys: uploads them, looks
+        them up, synchronises and downloads. rows is int64 (NO_ROW where the
+        key is absent), found a bool array."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        assert keys.ndim == 1
+        n = keys.shape[0]
+        if n == 0:
+            self._handle()
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=bool)
+        # device memory: a scratch context's columns (the C ABI has no allocator)
+        with Context(self._ctx.device) as donor:
+            donor.upload_columns(SIDE_PROBE, keys, np.zeros(n, dtype=np.int64))
+            donor.upload_columns(SIDE_BUILD, np.zeros((n + 7) // 8, dtype=np.int64))
+            kp, rp, _ = donor.columns_ptr(SIDE_PROBE)
+            fp = donor.columns_ptr(SIDE_BUILD)[0]
+            self.lookup(kp, n, rp, fp)
+            self._ctx.synchronize()
+            rows = np.ascontiguousarray(donor.download(SIDE_PROBE)[:, 1])
+            found = np.ascontiguousarray(donor.download(SIDE_BUILD)[:, 0]).view(np.uint8)[:n].astype(bool)
+        return rows, found
+
+    def close(self):
+        c = self._ctx
+        if self._h and c._h:
+            c._L.phj_index_destroy(c._h, self._h)
+            if self in getattr(c, "_indexes", []):
+                c._indexes.remove(self)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -46,6 +46,7 @@ EXPORTED = [
     "phj_relation_columns", "phj_relation_info_get",
     "phj_join_indices", "phj_joined_indices", "phj_joined_indices_download", "phj_gather_column",
     "phj_join_member",
+    "phj_index_build", "phj_index_info_get", "phj_index_lookup", "phj_index_destroy",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
@@ -121,6 +122,16 @@ class MemberCounts(C.Structure):
 
     def as_dict(self):
         return {"probe_matched": self.probe_matched, "build_matched": self.build_matched}
+
+
+class IndexInfo(C.Structure):
+    """phj_index_info: what a retained key index holds and its table's geometry."""
+    _fields_ = [("rows", C.c_uint64), ("distinct", C.c_uint64), ("table_bytes", C.c_uint64),
+                ("nb", C.c_uint32), ("nbr", C.c_uint32), ("rbits", C.c_uint32), ("slots", C.c_uint32)]
+
+    def as_dict(self):
+        return {"rows": self.rows, "distinct": self.distinct, "table_bytes": self.table_bytes,
+                "nb": self.nb, "nbr": self.nbr, "rbits": self.rbits, "slots": self.slots}
 
 
 class GroupRow(C.Structure):
@@ -229,6 +240,10 @@ def load():
         "phj_gather_column": (i, [P, P, u64, P, u64, C.POINTER(i64), P]),
         "phj_join_member": (i, [P, C.POINTER(JoinParams), C.c_uint32, P, P, C.POINTER(JoinResult),
                                 C.POINTER(MemberCounts)]),
+        "phj_index_build": (i, [P, C.POINTER(JoinParams), C.POINTER(P), C.POINTER(JoinResult)]),
+        "phj_index_info_get": (i, [P, C.POINTER(IndexInfo)]),
+        "phj_index_lookup": (i, [P, P, P, C.c_uint32, u64, P, P, P]),
+        "phj_index_destroy": (None, [P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

@@ -64,6 +64,7 @@
 #include "phj_hot.h"
 #include "phj_table.h"
 #include "phj_member.h"
+#include "phj_lookup.h"
 
 using namespace phj;
 
@@ -274,6 +275,20 @@ struct phj_ctx {
     hipEvent_t hot_fork = nullptr, hot_join = nullptr;
     uint32_t p1_free_cus = 0;
     bool p1_cols = false;   // the chunked pass 1 launched next reads a key column (partition_state, cols_native)
+    std::vector<phj_index*> indexes;   // phj_index_build: the live indexes (each owns its table; destroy frees survivors)
+};
+
+// A retained key index (phj_lookup.h): its table is memory of its own, not
+// workspace, so no later join, rebind or grow of the context touches it.
+struct phj_index {
+    phj_ctx* owner = nullptr;
+    IxBucket* tab = nullptr;
+    size_t bytes = 0;
+    NPHome g{};
+    int hk = 0;
+    uint64_t seed = 0;
+    uint64_t rows = 0, distinct = 0;
+    uint32_t max_wgs = 1;   // workgroups that fill the chip once at the lookup's occupancy
 };
 
 namespace {
@@ -2289,6 +2304,202 @@ int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipE
     return PHJ_OK;
 }
 
+// phj_index_build (phj_lookup.h): np_build's schedule over buckets of five
+// {code, row} entries. R is partitioned by region with its row numbers as the
+// payload (keys only, nothing packed), one workgroup per region finds or
+// claims in LDS, the overflow list follows with device atomics. The table is
+// the index's own allocation; the partition and the overflow list are the
+// context's workspace and are free again when the call returns.
+int index_geometry(phj_ctx* c, uint64_t rows, double table_ratio, NPHome& g) {
+    const double ratio = table_ratio > 0 ? table_ratio : kNPDefaultRatio;
+    if (ratio < 1.0) return set_err(c, PHJ_ERR_INVALID, "table_ratio must be >= 1");
+    const double nbd = std::ceil(static_cast<double>(std::max<uint64_t>(1, rows)) * ratio / kIxSlots);
+    if (nbd >= 4294967295.0) return set_err(c, PHJ_ERR_RANGE, "phj_index_build: table too large");
+    const uint32_t nb0 = std::max<uint32_t>(1, static_cast<uint32_t>(nbd));
+    g = NPHome{nb0, nb0, 0, 0};
+    g.rbits = std::min<uint32_t>(22, std::max<uint32_t>(1, ceil_log2((nb0 + kIxRegionBuckets - 1) / kIxRegionBuckets)));
+    g.nbr = (nb0 + (1u << g.rbits) - 1) >> g.rbits;
+    const uint64_t nbw = static_cast<uint64_t>(g.nbr) << g.rbits;
+    // (a region of more than kIxRegionBuckets buckets would need 2^22 regions of them: beyond 2^32 buckets)
+    if (nbw >= 4294967295ull || g.nbr > kIxRegionBuckets) return set_err(c, PHJ_ERR_RANGE, "phj_index_build: table too large");
+    g.nb = static_cast<uint32_t>(nbw);
+    return PHJ_OK;
+}
+
+int index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_result* r) {
+    const char* what = "phj_index_build";
+    if (!c || !out || !r) return PHJ_ERR_INVALID;
+    *out = nullptr;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    (void)hipGetLastError();
+    if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
+    if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
+        return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
+    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3) return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
+    if (p->algo == PHJ_ALGO_RADIX) {   // the usual validation; the plan itself is not used
+        Plan asked;
+        PHJ_TRY(make_plan(c, p, asked));
+    }
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    if (!R.rel && !R.columns && R.n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
+    if (R.n >= (1ull << 30)) return set_err(c, PHJ_ERR_RANGE, std::string(what) + ": build side of 2^30 rows or more");
+    NPHome g{};
+    PHJ_TRY(index_geometry(c, R.n, p->table_ratio, g));
+    PHJ_HIP(c, hipSetDevice(c->device));
+    std::memset(r, 0, sizeof(*r));
+    c->defer_timers = false;
+    c->lean_timers = false;
+    c->timer_skipped = false;
+    c->count_pinned = false;
+    c->ks = c->stream;
+    reset_timers(c);
+    const uint32_t nb = g.nb;
+    if (R.n > 0) {   // the workspace first: a grow synchronises, and nothing of the index exists yet
+        PHJ_TRY(ensure(c, c->count, 32));
+        PHJ_TRY(ensure(c, c->np_ovf, R.n * 16));
+        PHJ_TRY(ensure(c, c->np_ovfb, R.n * 4));
+        PHJ_TRY(ensure(c, c->np_ovfn, 4));
+    }
+    phj_index* ix = new phj_index();
+    ix->owner = c;
+    ix->g = g;
+    ix->hk = p->hash;
+    ix->seed = p->hash_seed;
+    ix->rows = R.n;
+    ix->bytes = static_cast<size_t>(nb) * sizeof(IxBucket);
+    auto fail = [&](int rc) {
+        if (ix->tab) (void)hipFree(ix->tab);
+        delete ix;
+        return rc;
+    };
+    {
+        void* mem = nullptr;
+        const hipError_t e = hipMalloc(&mem, ix->bytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(set_err(c, PHJ_ERR_NOMEM, "hipMalloc(" + std::to_string(ix->bytes) + "): " + hipGetErrorString(e)));
+        }
+        ix->tab = static_cast<IxBucket*>(mem);
+    }
+#define PHJ_IX(expr)                          \
+    do {                                      \
+        const int rc_ix_ = (expr);            \
+        if (rc_ix_ != PHJ_OK) return fail(rc_ix_); \
+    } while (0)
+    auto hip = [&](hipError_t e, const char* call) {
+        return e == hipSuccess ? PHJ_OK : set_err(c, PHJ_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
+    };
+    if (c->poison >= 0)   // (test hook) the region build writes every bucket before anything reads one
+        PHJ_IX(hip(hipMemsetAsync(ix->tab, c->poison, ix->bytes, c->ks), "hipMemsetAsync"));
+    const void* kfn = with_hash(p->hash, [&](auto h) {
+        return reinterpret_cast<const void*>(&k_ix_lookup<decltype(h)::value, 1>);   // (both strides share a resource shape)
+    });
+    int per_cu = occupancy(kfn, 256, 0);
+    if (per_cu < 1) per_cu = 4;
+    ix->max_wgs = static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(std::max(1, c->num_cus));
+    if (R.n == 0) {   // a valid index over nothing: every bucket empty, every lookup misses
+        PHJ_IX(hip(hipMemsetAsync(ix->tab, 0, ix->bytes, c->ks), "hipMemsetAsync"));
+        PHJ_IX(hip(hipStreamSynchronize(c->ks), "hipStreamSynchronize"));
+        c->indexes.push_back(ix);
+        *out = ix;
+        return PHJ_OK;
+    }
+    Plan rp;
+    {
+        phj_join_params pp = *p;
+        pp.algo = PHJ_ALGO_RADIX;
+        pp.num_partitions = 0;
+        pp.flags = 0;
+        pp.radix_bits[1] = static_cast<uint8_t>(g.rbits <= 8 ? 0 : g.rbits / 2);
+        pp.radix_bits[0] = static_cast<uint8_t>(g.rbits - pp.radix_bits[1]);
+        PHJ_IX(make_plan(c, &pp, rp));
+    }
+    hipEvent_t e0, e1;
+    PHJ_IX(mark(c, &e0));
+    PHJ_IX(partition_side(c, PHJ_SIDE_BUILD, rp, false, nullptr, PaySrc::RowNumber));
+    const phj_partitioned& v = R.view;
+    auto* cnt = static_cast<unsigned long long*>(c->count.p);
+    auto* ovn = static_cast<uint32_t*>(c->np_ovfn.p);
+    auto* ov = static_cast<ulonglong2*>(c->np_ovf.p);
+    auto* ovb = static_cast<uint32_t*>(c->np_ovfb.p);
+    // algorithmic bytes: the partitioned keys and rows read (16 B per tuple), every bucket written
+    PHJ_IX(timer_begin(c, "index.build", R.n * 16 + static_cast<uint64_t>(nb) * 64));
+    PHJ_IX(hip(hipMemsetAsync(cnt, 0, 16, c->ks), "hipMemsetAsync"));
+    PHJ_IX(hip(hipMemsetAsync(ovn, 0, 4, c->ks), "hipMemsetAsync"));
+    {
+        const size_t lds = static_cast<size_t>(g.nbr) * sizeof(IxBucket);
+        IxBucket* tab = ix->tab;
+        with_hash(p->hash, [&](auto h) {
+            hipLaunchKernelGGL((k_ix_build_region<decltype(h)::value>), dim3(1u << g.rbits), dim3(kBlock), lds, c->ks, v.keys,
+                               v.payloads, v.bounds, g, tab, p->hash_seed, ovn, ov, ovb, cnt);
+        });
+        c->since_ev++;
+        PHJ_IX(hip(hipGetLastError(), "launch k_ix_build_region"));
+        hipLaunchKernelGGL(k_ix_build_overflow, dim3(64), dim3(kBlock), 0, c->ks, ovn, ov, ovb, tab, nb, cnt);
+        c->since_ev++;
+        PHJ_IX(hip(hipGetLastError(), "launch k_ix_build_overflow"));
+    }
+    PHJ_IX(timer_end(c));
+    PHJ_IX(mark(c, &e1));
+    unsigned long long h[2] = {0, 0};   // {distinct codes, the overflow pass gave up on a tuple}
+    PHJ_IX(hip(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->ks), "hipMemcpyAsync"));
+    PHJ_IX(hip(hipStreamSynchronize(c->ks), "hipStreamSynchronize"));
+    if (h[1]) return fail(set_err(c, PHJ_ERR_STATE, std::string(what) + ": the table had no room for a key"));
+#undef PHJ_IX
+    ix->distinct = h[0];
+    r->matches = h[0];
+    r->partition_ms = 0;
+    r->build_ms = elapsed(c, e0, e1);
+    r->probe_ms = 0;
+    r->total_ms = elapsed(c, e0, e1);
+    r->num_partitions = 0;
+    const int rc = fill_timers(c, r);
+    if (rc != PHJ_OK) return fail(rc);
+    for (uint32_t i = 0; i < r->num_timers; i++) r->algorithmic_bytes += r->timer_bytes[i];   // R's passes and the build
+    c->indexes.push_back(ix);
+    *out = ix;
+    return PHJ_OK;
+}
+
+// phj_index_lookup: one launch on the context's stream and nothing else: no
+// event, no allocation, no copy back, no synchronisation.
+int index_lookup(phj_ctx* c, const phj_index* ix, const int64_t* keys, uint32_t key_stride, uint64_t n, int64_t* out_rows,
+                 uint8_t* out_found, unsigned long long* dev_found_count) {
+    const char* what = "phj_index_lookup";
+    if (!c || !ix) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    if (ix->owner != c) return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": the index belongs to another context");
+    if (key_stride != 1 && key_stride != 2)
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": key_stride must be 1 (a key column) or 2 (the ids of tuples)");
+    if (n == 0) return PHJ_OK;
+    if (!keys || !out_rows) return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": null keys or out_rows");
+    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_rows) |
+         reinterpret_cast<uintptr_t>(dev_found_count)) & 7)
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": keys, out_rows and the counter need 8-byte alignment");
+    (void)hipGetLastError();
+    PHJ_HIP(c, hipSetDevice(c->device));
+    IxLookupArgs a{};
+    a.keys = keys;
+    a.n = n;
+    a.tab = ix->tab;
+    a.g = ix->g;
+    a.seed = ix->seed;
+    a.rows = out_rows;
+    a.found = out_found;
+    a.count = dev_found_count;
+    const void* kfn = with_hash(ix->hk, [&](auto h) {
+        constexpr int HK = decltype(h)::value;
+        return key_stride == 1 ? reinterpret_cast<const void*>(&k_ix_lookup<HK, 1>)
+                               : reinterpret_cast<const void*>(&k_ix_lookup<HK, 2>);
+    });
+    const uint64_t per = 256ull * kIxItems;
+    const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((n + per - 1) / per, ix->max_wgs)));
+    void* kargs[] = {&a};
+    PHJ_HIP(c, hipLaunchKernel(kfn, dim3(grid), dim3(256), kargs, 0, c->stream));
+    PHJ_LAUNCHED(c, "k_ix_lookup");
+    return PHJ_OK;
+}
+
 // marks != nullptr: the probe also writes, per probe tuple, its match's payload
 // slot (phj_join_materialize)
 int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32_t* marks = nullptr) {
@@ -3480,6 +3691,10 @@ void phj_ctx_destroy(phj_ctx* c) {
     for (DevBuf* b : {&c->ht_tab, &c->ht_desc, &c->r_codes, &c->r_bounds, &c->scan_partials, &c->prep, &c->tkeys, &c->tpays, &c->toffs, &c->gcursor, &c->items, &c->biglist,
                       &c->count, &c->np_tab, &c->np_pays, &c->np_ovf, &c->np_ovfb, &c->np_ovfn, &c->fitems, &c->split, &c->cl_prof, &c->mat_mark, &c->mat_cnt, &c->mat_rows, &c->row_hit, &c->row_only, &c->row_cnt, &c->agg_acc, &c->agg_cnt, &c->agg_rows, &c->agg_res, &c->cl_done, &c->hot, &c->gather_bad, &c->member_marks})
         free_buf(*b);
+    for (phj_index* ix : c->indexes) {
+        if (ix->tab) (void)hipFree(ix->tab);
+        delete ix;
+    }
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
     for (hipEvent_t e : {c->hot_fork, c->hot_join})
         if (e) (void)hipEventDestroy(e);
@@ -4381,6 +4596,41 @@ static_assert(sizeof(phj_member_counts) == 16, "phj_member_counts layout");
 int phj_join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* probe_mask, uint8_t* build_mask,
                     phj_join_result* r, phj_member_counts* n) {
     return join_member(c, p, sides, probe_mask, build_mask, r, n);
+}
+
+// ---- the retained key index (phj_lookup.h) ----
+static_assert(sizeof(phj_index_info) == 40, "phj_index_info layout");
+
+int phj_index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_result* r) {
+    return index_build(c, p, out, r);
+}
+
+int phj_index_info_get(const phj_index* ix, phj_index_info* out) {
+    if (!ix || !out) return PHJ_ERR_INVALID;
+    out->rows = ix->rows;
+    out->distinct = ix->distinct;
+    out->table_bytes = ix->bytes;
+    out->nb = ix->g.nb;
+    out->nbr = ix->g.nbr;
+    out->rbits = ix->g.rbits;
+    out->slots = kIxSlots;
+    return PHJ_OK;
+}
+
+int phj_index_lookup(phj_ctx* c, const phj_index* ix, const int64_t* dev_keys, uint32_t key_stride, uint64_t n,
+                     int64_t* out_rows, uint8_t* out_found, unsigned long long* dev_found_count) {
+    return index_lookup(c, ix, dev_keys, key_stride, n, out_rows, out_found, dev_found_count);
+}
+
+void phj_index_destroy(phj_ctx* c, phj_index* ix) {
+    if (!c || !ix) return;
+    auto it = std::find(c->indexes.begin(), c->indexes.end(), ix);
+    if (it == c->indexes.end()) return;
+    c->indexes.erase(it);
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);   // lookups still in the stream read the table
+    if (ix->tab) (void)hipFree(ix->tab);
+    delete ix;
 }
 
 int phj_probe_pass1(phj_ctx* c, const phj_join_params* p, int64_t* keys, uint64_t n, uint32_t* bounds1,

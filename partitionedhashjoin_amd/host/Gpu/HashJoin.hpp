@@ -29,6 +29,12 @@
 // `probe_matched`, `build_matched` and, per asked side, `probe_mask_checksum`
 // / `build_mask_checksum` = Σ (i + 1) · mask[i] mod 2^64 are added to the
 // results; the returned table is empty, matches = probe_matched.
+// GpuConfiguration::Lookup asks for the retained key index instead of a join
+// (internal::join_lookup: phj_index_build over tableA once, phj_index_lookup
+// of tableB's keys in that many slices): `keys_looked_up`, `keys_found`,
+// `index_distinct`, `index_build_us`, `lookup_batch_us` and
+// `lookup_rows_checksum` = Σ (i + 1) · (row[i] + 1) mod 2^64 are added to the
+// results; the returned table is empty, matches = keys_found.
 // GpuConfiguration::Columns binds both relations as key / payload columns
 // (phj_relation_to_columns) before whatever was asked for runs; the results'
 // `layout` says which binding ran.
@@ -41,6 +47,7 @@
 // CLI catches and turns into exit(1) (src/main.cpp:277-281).
 #pragma once
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -198,6 +205,70 @@ inline void join_member(Device& dev, const phj_join_params& p, phj_join_result& 
     }
 }
 
+// --lookup BATCHES: a retained key index over tableA (phj_index_build, once),
+// then tableB's keys looked up in BATCHES equal slices, enqueued back to back
+// with one synchronise at the end (phj_index_lookup reads the bound probe
+// relation's memory as a plain device pointer: the key column, or the tuples'
+// ids at stride 2). The rows column and the found counter are columns of a
+// scratch context (the C ABI has no allocator). r is the build's result with
+// matches = the keys found (== the count join's matches) and probe_ms = the
+// wall time of all lookups.
+inline void join_lookup(Device& dev, const phj_join_params& p, phj_join_result& r, uint32_t batches,
+                        Common::IHashJoinTimer& timer) {
+    phj_ctx* c = dev.Get();
+    uint64_t nS = 0;
+    const int64_t *sk = nullptr, *sp = nullptr;
+    uint32_t stride = 1;
+    dev.Check(phj_relation_columns(c, PHJ_SIDE_PROBE, &sk, &sp, &nS));
+    if (!sk) {
+        sk = reinterpret_cast<const int64_t*>(phj_relation_device_ptr(c, PHJ_SIDE_PROBE, &nS));
+        stride = 2;
+    }
+    phj_index* ix = nullptr;
+    dev.Check(phj_index_build(c, &p, &ix, &r));
+    phj_index_info info{};
+    dev.Check(phj_index_info_get(ix, &info));
+    Device scratch(dev.DeviceId());
+    const std::vector<int64_t> zeros(std::max<uint64_t>(1, nS), 0);
+    scratch.Check(phj_relation_upload_columns(scratch.Get(), PHJ_SIDE_BUILD, zeros.data(), nullptr, zeros.size()));
+    scratch.Check(phj_relation_upload_columns(scratch.Get(), PHJ_SIDE_PROBE, zeros.data(), nullptr, 1));
+    const int64_t *rows_c = nullptr, *cnt_c = nullptr;
+    scratch.Check(phj_relation_columns(scratch.Get(), PHJ_SIDE_BUILD, &rows_c, nullptr, nullptr));
+    scratch.Check(phj_relation_columns(scratch.Get(), PHJ_SIDE_PROBE, &cnt_c, nullptr, nullptr));
+    int64_t* rows = const_cast<int64_t*>(rows_c);
+    auto* cnt = reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(cnt_c));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t b = 0; b < batches; b++) {
+        const uint64_t lo = nS * b / batches, hi = nS * (b + 1) / batches;
+        dev.Check(phj_index_lookup(c, ix, sk ? sk + stride * lo : nullptr, stride, hi - lo, rows + lo, nullptr, cnt));
+    }
+    dev.Check(phj_ctx_synchronize(c));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<phj_tuple> t(zeros.size());
+    scratch.Check(phj_relation_download(scratch.Get(), PHJ_SIDE_BUILD, t.data(), t.size()));
+    uint64_t sum = 0, hits = 0;
+    for (uint64_t i = 0; i < nS; i++) {
+        sum += (i + 1) * static_cast<uint64_t>(t[i].id + 1);
+        hits += t[i].id != PHJ_NO_ROW ? 1 : 0;
+    }
+    phj_tuple found{};
+    scratch.Check(phj_relation_download(scratch.Get(), PHJ_SIDE_PROBE, &found, 1));
+    phj_index_destroy(c, ix);
+    if (static_cast<uint64_t>(found.id) != hits)
+        throw std::runtime_error("--lookup: the device's found count differs from the rows it wrote");
+    timer.AddResult("batches", std::to_string(batches));
+    timer.AddResult("keys_looked_up", std::to_string(nS));
+    timer.AddResult("keys_found", std::to_string(hits));
+    timer.AddResult("index_rows", std::to_string(info.rows));
+    timer.AddResult("index_distinct", std::to_string(info.distinct));
+    timer.AddResult("index_table_bytes", std::to_string(info.table_bytes));
+    timer.AddResult("index_build_us", std::to_string(static_cast<int64_t>(std::llround(r.build_ms * 1e3))));
+    timer.AddResult("lookup_batch_us", std::to_string(static_cast<int64_t>(std::llround(ms * 1e3 / batches))));
+    timer.AddResult("lookup_rows_checksum", std::to_string(sum));
+    r.matches = hits;
+    r.probe_ms = ms;
+}
+
 // phj_join or, with rows requested, phj_join_materialize (one row per matching
 // probe tuple) / phj_join_inner (all: one row per pair) + the rows copied into
 // the returned table; with gpu.RowClasses, phj_join_rows of that kind
@@ -206,6 +277,10 @@ inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, con
                                                                 const Common::GpuConfiguration& gpu,
                                                                 Common::IHashJoinTimer& timer) {
     const bool materialize = gpu.Materialize, all = gpu.MaterializeAll;
+    if (gpu.Lookup != 0) {
+        join_lookup(dev, p, r, gpu.Lookup, timer);
+        return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());
+    }
     if (gpu.Member != 0) {
         join_member(dev, p, r, gpu.Member, timer);
         return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());

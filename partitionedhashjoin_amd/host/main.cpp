@@ -21,6 +21,7 @@
 //   --layout L            tuples|columns: bind the relations as {id, payload} tuples or as key / payload columns
 //   --rows W              payloads|indices: how the returned rows are made (indices: an index join on the key columns, then gathers)
 //   --member M            probe|build|both: report which rows have a partner on the other side (counts and mask checksums)
+//   --lookup BATCHES      build a retained key index over tableA once, look tableB's keys up in BATCHES equal slices
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -90,6 +91,13 @@ const char* kHelp =
     "                                      probe_matched, build_matched and, per asked side, a checksum of its mask,\n"
     "                                      sum of (i + 1) * mask[i] modulo 2^64. One device only, and not together\n"
     "                                      with returned rows or aggregates.\n"
+    "  --lookup arg                        BATCHES >= 1: build a retained key index over the primary relation once\n"
+    "                                      (phj_index_build), then look the secondary relation's keys up in BATCHES\n"
+    "                                      equal slices (phj_index_lookup, enqueued back to back): keys_looked_up,\n"
+    "                                      keys_found (the count join's matches), index_distinct, index_build_us,\n"
+    "                                      lookup_batch_us and a checksum of the rows, sum of (i + 1) * (row[i] + 1)\n"
+    "                                      modulo 2^64. One device only, and not together with returned rows,\n"
+    "                                      aggregates or membership masks.\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
@@ -124,7 +132,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
     static const std::set<std::string> known = {"help", "primary", "secondary", "skew", "log", "join", "format",
                                                 "unit", "output", "filename", "partitions", "device", "gpus", "devices", "exchange", "hash",
                                                 "radix-bits", "seed", "hash-seed", "generate", "table-ratio",
-                                                "materialize", "join-kind", "aggregate", "layout", "rows", "member"};
+                                                "materialize", "join-kind", "aggregate", "layout", "rows", "member", "lookup"};
     Common::Configuration c{};
     c.OutputFormatConfig.TimeUnit = "ms";
     c.OutputConfig.File.Name = "hashjoin.txt";
@@ -211,6 +219,11 @@ Common::Configuration parseArguments(int argc, char** argv) {
             else if (vm["member"] == "both") c.GpuConfig.Member = PHJ_MEMBER_PROBE | PHJ_MEMBER_BUILD;
             else throw std::invalid_argument("the argument ('" + vm["member"] + "') for option '--member' is invalid");
         }
+        if (vm.count("lookup")) {
+            const long long b = parse_number<long long>("lookup", vm["lookup"]);
+            if (b < 1 || b > 1000000) throw std::invalid_argument("--lookup takes 1..1000000 batches");
+            c.GpuConfig.Lookup = static_cast<uint32_t>(b);
+        }
         c.GpuConfig.Hash = PHJ_HASH_XXH3;
         if (vm.count("hash")) {
             if (vm["hash"] == "xxh3" || vm["hash"] == "xxhash") c.GpuConfig.Hash = PHJ_HASH_XXH3;
@@ -279,6 +292,12 @@ Common::Configuration parseArguments(int argc, char** argv) {
                 "--member returns no rows: not together with --materialize on / all, --join-kind, --aggregate or --rows");
         if (c.GpuConfig.Member && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--member runs on one device");
+        if (c.GpuConfig.Lookup && (c.GpuConfig.Materialize || c.GpuConfig.MaterializeAll || c.GpuConfig.RowClasses ||
+                                   c.GpuConfig.Aggregate || vm.count("rows") || c.GpuConfig.Member))
+            throw std::invalid_argument(
+                "--lookup returns no rows: not together with --materialize on / all, --join-kind, --aggregate, --rows or --member");
+        if (c.GpuConfig.Lookup && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
+            throw std::invalid_argument("--lookup runs on one device");
         if (c.GpuConfig.Columns && (c.GpuConfig.Devices.size() > 1 || c.GpuConfig.ContextFlags))
             throw std::invalid_argument("--layout columns runs on one device");
         if (c.GpuConfig.RowsAsIndices && !c.GpuConfig.RowClasses && !c.GpuConfig.MaterializeAll)
