@@ -723,22 +723,25 @@ int scan_u32(phj_ctx* c, uint32_t* data, uint32_t len, uint32_t narrays, uint32_
 // per thread only: cols_native).
 template <int HK, int DPT>
 const void* pipe1024(int kpf, bool hot = false, int cols = 0) {
+    // the HOT forms: batched by default (k_chunk_codes_pipe BATCH; -DPHJ_P1_BATCH=0: the per-tile form)
+    constexpr int kBatch = PHJ_PREAGG != 0 && PHJ_P1_BATCH != 0 ? 1 : 0;
+    (void)kBatch;
     if constexpr (DPT == 1 && PHJ_COL_LOAD16 != 0) {
         if (cols == 2) {
-            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, PHJ_PREAGG != 0 ? 1 : 0, 2>);
+            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, PHJ_PREAGG != 0 ? 1 : 0, 2, kBatch>);
             if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 0, 2>);
             return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 0, 2>);
         }
     }
     if constexpr (DPT == 1) {
         if (cols != 0) {
-            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, PHJ_PREAGG != 0 ? 1 : 0, 1>);
+            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, PHJ_PREAGG != 0 ? 1 : 0, 1, kBatch>);
             if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 0, 1>);
             return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 0, 1>);
         }
     }
     if constexpr (DPT == 1 && PHJ_PREAGG != 0) {   // the HOT form (phj_hot.h): S's pass counts the hot codes' weights
-        if (hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 1>);
+        if (hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, 1, 0, kBatch>);
     }
     if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, false, 1>);
     return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, PHJ_P1_PROF != 0, 2>);
@@ -879,7 +882,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
             if (c->tune.p1_slots > 0) slots = std::min<uint32_t>(per, c->tune.p1_slots);
             if (c->tune.p1_slots < 0) slots = per;   // one tile per workgroup
             PassArgs ak = a;
-            const bool prof = PHJ_P1_PROF && pipe && kblock == 1024 && !is_r && !hot;
+            const bool prof = PHJ_P1_PROF && pipe && kblock == 1024 && !is_r && (hot || !cols_form);   // (the forms pipe1024 builds with PROF)
             if (prof) {   // diagnostics (measurement build, PHJ_P1_PROF): synchronous, to stderr
                 PHJ_TRY(ensure(c, c->cl_prof, 64 * 8));   // words 32.. (the LDS join's are 0..)
                 ak.prof = static_cast<unsigned long long*>(c->cl_prof.p) + 32;
@@ -892,6 +895,12 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                 PHJ_HIP(c, hipMemcpyAsync(h, ak.prof, sizeof(h), hipMemcpyDeviceToHost, c->ks));
                 PHJ_HIP(c, hipStreamSynchronize(c->ks));
                 const double n = h[7] ? static_cast<double>(h[7]) : 1.0;
+                if (h[15])   // the batched loop ran (the hot table on): its own phases
+                    std::fprintf(stderr, "p1_prof %s grid %u batched: cycles per input tile: front %.0f append %.0f protocol+wait at A %.0f write %.0f sort stage %.0f (the PROF forms: 128 VGPRs, XXH3 spills 2); "
+                                 "per batch: sort stage %.0f; tiles %llu batches %llu (%.3f per tile) iterations %llu\n",
+                                 sname.c_str(), slots * a.nshards, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n,
+                                 h[5] ? static_cast<double>(h[4]) / h[5] : 0.0, h[7], h[5], h[5] / n, h[14]);
+                else
                 std::fprintf(stderr, "p1_prof %s grid %u: cycles per tile: hash+rank %.0f B1 %.0f scan %.0f claims+B2 %.0f scatter+protocol %.0f B3 %.0f write %.0f; tiles %llu; "
                              "waves' max/mean B3->B1 %.0f/%.0f B1->B2 %.0f/%.0f B2->B3 %.0f/%.0f\n",
                              sname.c_str(), slots * a.nshards, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[5] / n, h[6] / n, h[7],

@@ -156,6 +156,9 @@ constexpr uint32_t kHotWays = 2, kHotSub = 2, kHotPer = kHotWays * kHotSub;
 #ifndef PHJ_HOT_FUSE   // S's pass, HOT 1: a code's weight add and rank claim are one LDS atomic (0: two, the A/B leg)
 #define PHJ_HOT_FUSE 1
 #endif
+#ifndef PHJ_P1_BATCH   // S's pass, HOT 1: the sort stage once per T kept codes (0: once per input tile, the A/B leg)
+#define PHJ_P1_BATCH 1
+#endif
 constexpr uint32_t kHotCtlEntries = 0, kHotCtlMass = 1;   // hot_ctl words: entries, sampled keys they cover
 
 // Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md,
@@ -1152,7 +1155,10 @@ __host__ __device__ constexpr size_t chunk_pipe_lds_bytes(int T, uint32_t nb) {
     return 2 * static_cast<size_t>(T) * 8 + (static_cast<size_t>(2 * nb + 3) / 4 * 4 + 4 * static_cast<size_t>(nb)) * 4 + 128;
 }
 // ... and after them the HOT form's copy of the hot table: the codes, the
-// workgroup's 32-bit weights and a word per thread (1024 of them)
+// workgroup's 32-bit weights and a word per thread (1024 of them: hown[],
+// the target of the per-tile loop's adds of 0. The batched loop does not use
+// it, but a BATCH kernel still runs the per-tile loop with its HOT 1 adds when
+// the table is off at run time, so the 4 KB stay in every HOT form)
 __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int hot) {
     return hot == 0 ? 0 : static_cast<size_t>(nb) * kHotPer * 12 + 4096;
 }
@@ -1179,6 +1185,28 @@ __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int h
 // covers 512 contiguous bytes); 2: 16 B, two neighbouring keys per lane, half
 // the load instructions, items 2p and 2p + 1 of a lane then being neighbours
 // (pipe_elem). 0: tuples, the code as before the column forms.
+// BATCH (HOT 1 with the table on at run time; off: the per-tile loop below):
+// the sort stage (rank, scan, claims, LDS scatter, protocol, write-out) runs
+// once per T KEPT codes, not once per input tile. A loop iteration is still
+// one input tile: hash, lookups, weight adds (no return value), and every kept
+// code gets the next index g among the workgroup's kept codes (ballot / mbcnt
+// prefix in the wave, one LDS atomic per wave) and goes to sbuf[g mod 2T]: the
+// two sorted-tile buffers are one ring, batch b = indices [bT, (b + 1)T) lies
+// in half b & 1 and uses counter row and reservation words b & 1. After the
+// iteration's one barrier (A) the ring's count is known; once it holds T codes
+// batch b closes: its T codes are read into registers, ranked, scanned,
+// claimed and scattered back into the same T slots (barriers B1, the scan's,
+// B2). Its claims are resolved in the very next iteration, batch or none
+// (publishes, waits, descriptor row before A, write-out after A): other
+// workgroups wait on those publishes. A kept code that falls past the closing
+// batch (index >= (b + 1)T, at most T - 1 of them) would land in the half that
+// batch b - 1 is still written out from, so it stays in registers until B1.
+// At most one batch closes per iteration and a workgroup closes no more
+// batches than it has tiles, so batch b takes the reserved chunk of the
+// workgroup's b-th tile. After the last tile the leftover (< T) closes as a
+// partial batch (the write-out's past() form) and is resolved in one more
+// iteration. Words tmp[21 + parity]: kept codes appended in the iterations of
+// that parity, never reset (read after A, added to again two iterations on).
 typedef long long key_pair __attribute__((ext_vector_type(2), aligned(8)));   // 16 B loaded from an 8-B aligned column
 // element of the tile that is item i of a lane
 template <int COLS>
@@ -1186,19 +1214,20 @@ __device__ __forceinline__ uint32_t pipe_elem(uint32_t wbase, uint32_t lane, int
     if constexpr (COLS == 2) return wbase + static_cast<uint32_t>(i >> 1) * 128 + lane * 2 + static_cast<uint32_t>(i & 1);
     else return wbase + i * 64 + lane;
 }
-template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0, int COLS = 0>
+template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0, int COLS = 0, int BATCH = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : BLOCK / 256)))
 void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     constexpr int NW = BLOCK / 64;
     constexpr int T = BLOCK * ITEMS;
     static_assert(NW <= 16, "scan words [0, NW) below the reservation words");
     static_assert(HOT == 0 || HOT == 1, "HOT 1: S's pre-aggregating pass");
+    static_assert(BATCH == 0 || (HOT == 1 && DPT == 1 && (T & (T - 1)) == 0), "BATCH: the HOT 1 form, one digit per thread, ring slot = index mod 2T");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t nb = a.nbins;   // host: nb <= DPT * BLOCK
     int64_t* sbuf = reinterpret_cast<int64_t*>(smem);                       // [2][T] sorted codes
     uint32_t* wcnt = reinterpret_cast<uint32_t*>(sbuf + 2 * T);             // [2][nb] counter rows
     uint4* wdesc = reinterpret_cast<uint4*>(wcnt + (2 * nb + 3u) / 4 * 4);  // [nb] {k < split: slot - k, else, split}
-    uint32_t* tmp = reinterpret_cast<uint32_t*>(wdesc + nb);                // [0, NW) scan; 16-19 reservations [2]; 20 bad tile
+    uint32_t* tmp = reinterpret_cast<uint32_t*>(wdesc + nb);                // [0, NW) scan; 16-19 reservations [2]; 20 bad tile; 21-22 BATCH: kept codes appended [parity]
     unsigned long long* hcode = reinterpret_cast<unsigned long long*>(tmp + 32);   // HOT: [nb][kHotPer] codes
     uint32_t* hwt = reinterpret_cast<uint32_t*>(hcode + static_cast<size_t>(nb) * kHotPer);   // HOT 1: their weights in this workgroup
     uint32_t* hown = hwt + static_cast<size_t>(nb) * kHotPer;   // HOT 1: [BLOCK] a word per lane for the adds of 0
@@ -1317,6 +1346,8 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                 hcode[i] = a.hot_code[i];
                 if constexpr (HOT == 1) hwt[i] = 0;
             }
+        if constexpr (BATCH != 0)
+            if (tid == 0) tmp[21] = tmp[22] = 0;   // (tmp[20] is reset by every close before it is read)
     }
     {
 #pragma unroll
@@ -1345,6 +1376,287 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     uint32_t pcnt = 0, par = 0;
     const uint32_t d0 = tid * DPT;
     if (PROF) pc0 = px = clock64();
+    if constexpr (BATCH != 0) {
+        if (hot) {   // (the header comment's batched loop; workgroup-uniform)
+            const uint32_t tile0 = tile;
+            uint32_t gtot = 0;            // kept codes appended before this iteration ...
+            uint32_t uns = 0;             // ... of which not yet in a closed batch (< T)
+            uint32_t nbat = 0;            // batches closed
+            uint32_t wprev[2] = {0, 0};   // tmp[21 + parity] as this parity's last iteration left it
+            bool pend = false;            // batch nbat - 1 is claimed and not yet written out ...
+            uint32_t plim = 0;            // ... its codes (T, or the drain's leftover)
+            // PROF words here (thread 0's clocks): 0 front, 1 append, 2 protocol
+            // and the wait at A (the other waves' fronts, protocols and spin
+            // waits), 3 write-out, 4 sort stage, 5 batches, 7 tiles, 14
+            // iterations, 15 workgroups. The PROF forms are at 128 VGPRs and the
+            // XXH3 ones spill 2 VGPRs (12 B of scratch): the clocks are those of
+            // a slightly heavier kernel than the shipped one (124 / 126 VGPRs)
+            auto biter = [&](auto kbc, auto cbc) -> bool {
+                constexpr int kb = decltype(kbc)::value, cb = decltype(cbc)::value;
+                uint32_t(&v0)[DPT] = cv0[cb];
+                unsigned long long(&hint)[DPT] = chint[cb];
+                const uint32_t(&pv0)[DPT] = cv0[cb ^ 1];
+                const unsigned long long(&phint)[DPT] = chint[cb ^ 1];
+                const bool live = tile < t_end;   // false: the drain
+                const uint32_t cnt = live ? min(static_cast<uint32_t>(T), a.n - tile * T) : 0u;
+                const uint32_t gsort = gtot - uns;   // first index of the batch being filled
+                int64_t code[ITEMS];
+                uint32_t gi[ITEMS];   // a kept code's index
+                uint32_t held = 0;    // bit i = item i is kept and past the batch being filled: stored after B1
+                if (live) {
+                    uint32_t dig[ITEMS];
+                    auto hash_all = [&](auto form, auto full) {
+#pragma unroll
+                        for (int i = 0; i < ITEMS; i++) {
+                            uint64_t h;
+                            if constexpr (COLS == 2 && !decltype(full)::value) {
+                                const bool tail = (i & 1) == 0 && pipe_elem<COLS>(wbase, lane, i) + 1 == cnt;
+                                h = hash64<HK>(static_cast<uint64_t>(tail ? key[kb][i | 1] : key[kb][i]), a.f.seed);
+                            } else {
+                                h = hash64<HK>(static_cast<uint64_t>(key[kb][i]), a.f.seed);
+                            }
+                            code[i] = static_cast<int64_t>(h);
+                            dig[i] = decltype(full)::value || pipe_elem<COLS>(wbase, lane, i) < cnt ? code_digit(h, form) : 0u;
+                        }
+                    };
+                    if (dform == 2 && cnt == static_cast<uint32_t>(T)) hash_all(F2{}, std::true_type{});
+                    else if (dform == 2) hash_all(F2{}, std::false_type{});
+                    else if (dform == 1) hash_all(F1{}, std::false_type{});
+                    else hash_all(F0{}, std::false_type{});
+                    const uint32_t ahead = tile + KPF * slots;
+                    load(key[kb], ahead < t_end ? ahead : tile);
+                    // every set read first, then the compares; a hot code adds 1
+                    // to its entry's weight (no return value) and is not kept
+                    uint32_t keep = 0;
+                    uint4 set[ITEMS];
+                    uint32_t e[ITEMS];
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) {
+                        keep |= (pipe_elem<COLS>(wbase, lane, i) < cnt ? 1u : 0u) << i;
+                        e[i] = dig[i] * kHotPer + static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 63) * kHotWays;
+                        set[i] = *reinterpret_cast<const uint4*>(hcode + e[i]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) {
+                        const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
+                        const bool m0 = set[i].x == lo && set[i].y == hi, m1 = set[i].z == lo && set[i].w == hi;
+                        const bool m = (m0 || m1) && ((keep >> i) & 1u) != 0;
+                        if (m) atomicAdd(&hwt[e[i] + (m0 ? 0u : 1u)], 1u);
+                        keep &= ~((m ? 1u : 0u) << i);
+                    }
+                    ptick(0);
+                    // append: the wave's kept codes take consecutive indices, one LDS atomic per wave
+                    uint32_t off[ITEMS], wtot = 0;
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) {
+                        const uint64_t b = __ballot(((keep >> i) & 1u) != 0);
+                        off[i] = wtot + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u));
+                        wtot += static_cast<uint32_t>(__popcll(b));
+                    }
+                    uint32_t wbase_g = 0;
+                    if (lane == 0) wbase_g = atomicAdd(&tmp[21 + cb], wtot);
+                    wbase_g = __builtin_amdgcn_readfirstlane(wbase_g) - wprev[cb] + gtot;
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) {
+                        gi[i] = wbase_g + off[i];
+                        const bool k = ((keep >> i) & 1u) != 0, now = k && gi[i] - gsort < static_cast<uint32_t>(T);
+                        if (now) sbuf[gi[i] & (2 * T - 1)] = code[i];
+                        held |= (k && !now ? 1u : 0u) << i;
+                    }
+                    ptick(1);
+                }
+                const uint32_t pp = (nbat - 1) & 1u;   // the pending batch's half, row and words
+                if (pend) {
+                    // the protocol of the per-tile loop below for the pending batch's
+                    // runs: publish (no waits), then resolve the ids, then the descriptor
+                    uint32_t bad = 0;
+                    if (pc[0]) {
+                        const uint32_t d = d0;
+                        const uint32_t off = pv0[0] % T, k0 = pv0[0] / T, k1 = (pv0[0] + pc[0] - 1) / T;
+                        uint32_t st = 0xffffffffu, nid = 0;   // chunk this run starts (or ~0u) and the id it took for st + 1
+                        if (off == 0) st = k0;
+                        else if (k1 != k0) st = k1;
+                        unsigned long long* tab = a.chunk_tab + (static_cast<size_t>(x) * nb + d) * a.maxch;
+                        const uint32_t s0 = id_lo + 2 * d;   // static chunks 0, 1 of the chain
+                        if (st == 0) {
+                            nid = s0 + 1;
+                            if (a.maxch >= 2) {
+                                __hip_atomic_store(&tab[0], kPublished | s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                __hip_atomic_store(&tab[1], kPublished | (s0 + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            } else {
+                                bad |= kChunkErrIndex;
+                            }
+                        } else if (st != 0xffffffffu) {
+                            const uint32_t r = atomicAdd(&tmp[17 + 2 * pp], 1u);
+                            nid = r < kPipeRes ? tmp[16 + 2 * pp] + r : id_lo + 2 * nb + kPipeRes * per + atomicAdd(pool, 1u);
+                            if (st + 1 < a.maxch)
+                                __hip_atomic_store(&tab[st + 1], kPublished | nid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        const uint32_t hk = static_cast<uint32_t>(phint[0] >> 44);
+                        const uint32_t hid = phint[0] ? id_lo + (static_cast<uint32_t>(phint[0] >> 22) & 0x3fffffu) : s0;
+                        const uint32_t hid1 = phint[0] ? id_lo + (static_cast<uint32_t>(phint[0]) & 0x3fffffu) : s0 + 1;
+                        auto id_of = [&](uint32_t k) -> uint32_t {
+                            if (k == 0) return s0;
+                            if (k == 1) return s0 + 1;
+                            if (k == hk) return hid;
+                            if (k == hk + 1) return hid1;
+                            if (k >= a.maxch) {
+                                bad |= kChunkErrIndex;
+                                return id_lo;
+                            }
+                            unsigned long long v;
+                            while (((v = __hip_atomic_load(&tab[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 32) == 0)
+                                __builtin_amdgcn_s_sleep(2);
+                            return static_cast<uint32_t>(v);
+                        };
+                        const uint32_t id0 = id_of(k0);
+                        const uint32_t id1 = k1 != k0 ? id_of(k1) : id0;
+                        if (st != 0xffffffffu && st != 0) {
+                            const uint32_t ids = st == k0 ? id0 : id1;
+                            atomicMax(hints + d, pipe_hint(st, ids - id_lo, nid - id_lo));
+                        }
+                        if (id0 < id_lo || id0 >= id_hi || id1 < id_lo || id1 >= id_hi || nid >= id_hi) bad |= kChunkErrId;
+                        const uint32_t split = pds[0] + (T - off);
+                        wdesc[d] = make_uint4(id0 * T + off - pds[0], id1 * T - split, split, 0u);
+                    }
+                    if (bad) {
+                        tmp[20] = 1;
+                        atomicOr(errw, bad);
+                    }
+                }
+                __syncthreads();   // A: the appends, the pending batch's slots
+                ptick(2);
+                uint32_t k = 0;
+                if (live) {
+                    const uint32_t w = __builtin_amdgcn_readfirstlane(tmp[21 + cb]);
+                    k = w - wprev[cb];
+                    wprev[cb] = w;
+                }
+                const uint32_t tot = uns + k;   // the ring's unsorted codes
+                gtot += k;
+                const bool closes = live ? tot >= static_cast<uint32_t>(T) : tot != 0;
+                const uint32_t bcnt = min(tot, static_cast<uint32_t>(T));
+                if (pend) {
+                    const uint32_t lim = tmp[20] ? 0u : plim;
+                    auto write_out = [&](auto form, auto full) {
+                        int64_t v[ITEMS];
+                        uint32_t o[ITEMS];
+                        auto past = [&](int i) { return !decltype(full)::value && static_cast<uint32_t>(i) * BLOCK >= lim; };
+#pragma unroll
+                        for (int i = 0; i < ITEMS; i++)
+                            if (!past(i)) v[i] = sbuf[pp * T + i * BLOCK + tid];
+#pragma unroll
+                        for (int i = 0; i < ITEMS; i++) {
+                            if (past(i)) continue;
+                            const uint32_t s = i * BLOCK + tid;
+                            const uint4 w = wdesc[code_digit(static_cast<uint64_t>(v[i]), form)];
+                            o[i] = (s < w.z ? w.x : w.y) + s;
+                        }
+#pragma unroll
+                        for (int i = 0; i < ITEMS; i++) {
+                            if (past(i)) continue;
+                            if constexpr (decltype(full)::value) a.out_keys[o[i]] = v[i];
+                            else *(i * BLOCK + tid < lim ? a.out_keys + o[i] : ssink) = v[i];
+                        }
+                    };
+                    if (dform == 2 && lim == static_cast<uint32_t>(T)) write_out(F2{}, std::true_type{});
+                    else if (dform == 2) write_out(F2{}, std::false_type{});
+                    else if (dform == 1) write_out(F1{}, std::false_type{});
+                    else write_out(F0{}, std::false_type{});
+                }
+                ptick(3);
+                if (closes) {
+                    const uint32_t bp = nbat & 1u;
+                    uint32_t* const crow = wcnt + bp * nb;
+                    int64_t bc[ITEMS];
+                    uint32_t bd[ITEMS], rank[ITEMS];
+                    auto rank_all = [&](auto form, auto full) {
+#pragma unroll
+                        for (int i = 0; i < ITEMS; i++) bc[i] = sbuf[bp * T + i * BLOCK + tid];
+#pragma unroll
+                        for (int i = 0; i < ITEMS; i++) {
+                            const bool valid = decltype(full)::value || static_cast<uint32_t>(i) * BLOCK + tid < bcnt;
+                            bd[i] = valid ? code_digit(static_cast<uint64_t>(bc[i]), form) : 0u;
+                            rank[i] = 0;
+                            if (valid) rank[i] = atomicAdd(&crow[bd[i]], 1u);
+                        }
+                    };
+                    if (dform == 2 && bcnt == static_cast<uint32_t>(T)) rank_all(F2{}, std::true_type{});
+                    else if (dform == 2) rank_all(F2{}, std::false_type{});
+                    else if (dform == 1) rank_all(F1{}, std::false_type{});
+                    else rank_all(F0{}, std::false_type{});
+                    __syncthreads();   // B1: ranks counted; the pending batch's half is read
+                    if (tot > static_cast<uint32_t>(T)) {
+#pragma unroll
+                        for (int i = 0; i < ITEMS; i++)
+                            if ((held >> i) & 1u) sbuf[gi[i] & (2 * T - 1)] = code[i];
+                    }
+                    const uint32_t c = d0 < nb ? crow[d0] : 0u;
+                    uint32_t total;
+                    const uint32_t run = block_exclusive_scan_t<NW, false>(c, tmp, total);
+                    if (d0 < nb) {
+                        crow[d0] = run;
+                        wcnt[(bp ^ 1u) * nb + d0] = 0;   // the next batch's counter row
+                    }
+                    {   // claims of every digit (0 adds too): resolved next iteration
+                        const bool real = d0 < nb;
+                        uint32_t* cw = real ? curs + d0 : reinterpret_cast<uint32_t*>(ssink);
+                        unsigned long long* hw = real ? hints + d0 : reinterpret_cast<unsigned long long*>(ssink);
+                        v0[0] = atomicAdd(cw, real ? c : 0u);
+                        hint[0] = __hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                    if (tid == 0) {
+                        tmp[16 + 2 * bp] = id_lo + 2 * nb + kPipeRes * (tile0 + nbat * slots - x * per);   // the b-th tile's reserved chunks
+                        tmp[17 + 2 * bp] = 0;
+                        tmp[20] = 0;
+                    }
+                    __syncthreads();   // B2: batch-local starts, reservations
+                    uint32_t base[ITEMS];
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++) base[i] = crow[bd[i]];
+#pragma unroll
+                    for (int i = 0; i < ITEMS; i++)
+                        if (static_cast<uint32_t>(i) * BLOCK + tid < bcnt) sbuf[bp * T + base[i] + rank[i]] = bc[i];
+                    pc[0] = c;
+                    pds[0] = run;
+                    plim = bcnt;
+                    nbat++;
+                }
+                uns = tot - (closes ? bcnt : 0u);
+                pend = closes;
+                ptick(4);
+                if (PROF && tid == 0) {
+                    prof[PROF ? 5 : 0] += closes ? 1 : 0;
+                    prof[PROF ? 7 : 0] += live ? 1 : 0;
+                    prof[PROF ? 14 : 0] += 1;
+                }
+                if (!live && !pend) {
+                    if (PROF && tid == 0 && a.prof) {
+                        prof[PROF ? 15 : 0] = 1;
+                        for (int w = 0; w < kP1ProfWords; w++) atomicAdd(&a.prof[w], prof[PROF ? w : 0]);
+                    }
+                    return false;
+                }
+                if (live) tile += slots;
+                return true;
+            };
+            using B0 = std::integral_constant<int, 0>;
+            using B1 = std::integral_constant<int, 1>;
+            if constexpr (KPF == 1) {
+                while (biter(B0{}, B0{}) && biter(B0{}, B1{})) {
+                }
+            } else {
+                while (biter(B0{}, B0{}) && biter(B1{}, B1{})) {
+                }
+            }
+            // (every weight add is before barrier A of the drain's first iteration)
+            for (uint32_t i = tid; i < nb * kHotPer; i += BLOCK) {
+                const uint32_t w = hwt[i];
+                if (w) atomicAdd(&a.hot_w[i], static_cast<unsigned long long>(w));
+            }
+            return;
+        }
+    }
     auto iter = [&](auto kbc, auto cbc) -> bool {
         constexpr int kb = decltype(kbc)::value, cb = decltype(cbc)::value;
         uint32_t(&v0)[DPT] = cv0[cb];
