@@ -159,6 +159,25 @@ constexpr uint32_t kHotWays = 2, kHotSub = 2, kHotPer = kHotWays * kHotSub;
 #ifndef PHJ_P1_BATCH   // S's pass, HOT 1: the sort stage once per T kept codes (0: once per input tile, the A/B leg)
 #define PHJ_P1_BATCH 1
 #endif
+// The batched loop's front (hash to barrier A), one A/B leg each (0: as before):
+#ifndef PHJ_P1F_BUFLOAD  // the pipelined code pass's key loads (every form but COLS 2) as buffer loads off a per-tile scalar descriptor
+#define PHJ_P1F_BUFLOAD 1
+#endif
+#ifndef PHJ_P1F_SET128  // every set read is one 16-B LDS read (the compiler split item 0's and read its last word behind a branch)
+#define PHJ_P1F_SET128 1
+#endif
+#ifndef PHJ_P1F_WTADDR   // 1: a set's weights lie 16 B behind its codes, the weight add's address is the lookup's plus a constant (measured level, 16 KB more LDS at 1024 digits: off)
+#define PHJ_P1F_WTADDR 0
+#endif
+#ifndef PHJ_P1F_FULL     // a whole tile compiles no validity compare into the lookups and the append
+#define PHJ_P1F_FULL 1
+#endif
+#ifndef PHJ_P1F_CMPBALLOT // the kept codes' ballot put together from the ballots of the four plain compares of a lookup
+#define PHJ_P1F_CMPBALLOT 1
+#endif
+#ifndef PHJ_P1F_WAVEFAST // append: a wave whose indices all lie in the batch being filled does no range compare and holds nothing
+#define PHJ_P1F_WAVEFAST 1
+#endif
 constexpr uint32_t kHotCtlEntries = 0, kHotCtlMass = 1;   // hot_ctl words: entries, sampled keys they cover
 
 // Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md,
@@ -1159,8 +1178,14 @@ __host__ __device__ constexpr size_t chunk_pipe_lds_bytes(int T, uint32_t nb) {
 // the target of the per-tile loop's adds of 0. The batched loop does not use
 // it, but a BATCH kernel still runs the per-tile loop with its HOT 1 adds when
 // the table is off at run time, so the 4 KB stay in every HOT form)
+// PHJ_P1F_WTADDR: the table is laid by sets of kHotSetBytes: a set's kHotWays
+// codes (the 16-B read), their kHotWays weights, 8 B unused. The weight of a
+// matched way is then at the lookup's address + 16 + 4 * way: nothing to
+// rebuild from the table's base inside the exec-masked add. (0: all codes,
+// then all weights.)
+constexpr uint32_t kHotSetBytes = PHJ_P1F_WTADDR ? 32 : 12 * kHotWays;
 __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int hot) {
-    return hot == 0 ? 0 : static_cast<size_t>(nb) * kHotPer * 12 + 4096;
+    return hot == 0 ? 0 : static_cast<size_t>(nb) * kHotSub * kHotSetBytes + 4096;
 }
 
 // Registers: one workgroup per CU (LDS). WPE: waves per SIMD the registers
@@ -1207,7 +1232,21 @@ __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int h
 // partial batch (the write-out's past() form) and is resolved in one more
 // iteration. Words tmp[21 + parity]: kept codes appended in the iterations of
 // that parity, never reset (read after A, added to again two iterations on).
+// The front of an iteration (PHJ_P1F_*, each an A/B leg): after the hash and
+// the next tile's loads, a whole tile (cnt == T) takes a form of the lookups
+// and the append with no validity compare; the kept predicates stay lane
+// masks, and their ballots are put together in scalar registers from the
+// ballots of the lookup's four plain compares; a wave whose indices all lie
+// in the batch being filled (a wave-uniform test, no barrier inside) stores
+// at (scalar base) + 8 * mbcnt with no range compare and holds nothing, the
+// wave that crosses the batch's end takes the general path.
+// Key loads (PHJ_P1F_BUFLOAD, every form but COLS 2): buffer loads off a
+// descriptor built per tile in scalar registers (base = the tile's first
+// element: 64-bit, so relations beyond 4 GiB; size = the tile's valid bytes),
+// one per-lane offset and the items' distances as immediates. A lane past the
+// relation's end reads 0, never a tuple: validity comes from cnt alone.
 typedef long long key_pair __attribute__((ext_vector_type(2), aligned(8)));   // 16 B loaded from an 8-B aligned column
+typedef uint32_t hot_set_t __attribute__((ext_vector_type(4)));   // a set of the hot table: kHotWays 64-bit codes
 // element of the tile that is item i of a lane
 template <int COLS>
 __device__ __forceinline__ uint32_t pipe_elem(uint32_t wbase, uint32_t lane, int i) {
@@ -1228,9 +1267,17 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     uint32_t* wcnt = reinterpret_cast<uint32_t*>(sbuf + 2 * T);             // [2][nb] counter rows
     uint4* wdesc = reinterpret_cast<uint4*>(wcnt + (2 * nb + 3u) / 4 * 4);  // [nb] {k < split: slot - k, else, split}
     uint32_t* tmp = reinterpret_cast<uint32_t*>(wdesc + nb);                // [0, NW) scan; 16-19 reservations [2]; 20 bad tile; 21-22 BATCH: kept codes appended [parity]
-    unsigned long long* hcode = reinterpret_cast<unsigned long long*>(tmp + 32);   // HOT: [nb][kHotPer] codes
-    uint32_t* hwt = reinterpret_cast<uint32_t*>(hcode + static_cast<size_t>(nb) * kHotPer);   // HOT 1: their weights in this workgroup
-    uint32_t* hown = hwt + static_cast<size_t>(nb) * kHotPer;   // HOT 1: [BLOCK] a word per lane for the adds of 0
+    // HOT: the hot table's codes and (HOT 1) their weights in this workgroup
+    // (chunk_pipe_hot_lds_bytes). Set s = digit * kHotSub + the code's top
+    // bit; entry = s * kHotWays + way; byte offsets from hbase
+    unsigned char* const hbase = reinterpret_cast<unsigned char*>(tmp + 32);
+    auto hot_set_off = [&](uint32_t s) -> uint32_t { return PHJ_P1F_WTADDR ? s * kHotSetBytes : s * (kHotWays * 8); };
+    auto hot_wt_off = [&](uint32_t s, uint32_t way) -> uint32_t {
+        return PHJ_P1F_WTADDR ? s * kHotSetBytes + kHotWays * 8 + way * 4 : nb * kHotPer * 8 + (s * kHotWays + way) * 4;
+    };
+    auto hot_code = [&](uint32_t entry) { return reinterpret_cast<unsigned long long*>(hbase + hot_set_off(entry / kHotWays)) + entry % kHotWays; };
+    auto hot_wt = [&](uint32_t off) { return reinterpret_cast<uint32_t*>(hbase + off); };
+    uint32_t* hown = reinterpret_cast<uint32_t*>(hbase + static_cast<size_t>(nb) * kHotSub * kHotSetBytes);   // HOT 1: [BLOCK] a word per lane for the adds of 0
 
     const uint32_t x = blockIdx.x % a.nshards, slots = gridDim.x / a.nshards;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1302,7 +1349,44 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     // 8-B column form: a wave's load covers 64 consecutive elements. COLS 2:
     // a lane's 16-B load brings two neighbouring keys, items 2p and 2p + 1.
     static_assert(COLS == 0 || COLS == 1 || (COLS == 2 && ITEMS % 2 == 0), "COLS 2: whole pairs per lane");
+#if PHJ_P1F_BUFLOAD
+    // the lane's byte offset in a tile (made opaque at each use: the items'
+    // distances then stay constants added beside the load, which takes them
+    // as immediates, rather than four offsets hoisted into registers)
+    const uint32_t bvo0 = (wbase + lane) * (COLS == 1 ? 8u : 16u);
+#endif
     auto load = [&](int64_t* k, uint32_t t) {
+#if PHJ_P1F_BUFLOAD
+        if constexpr (COLS != 2) {
+            // buffer loads: the tile's descriptor in scalar registers (base =
+            // the tile's first element, so a relation beyond 4 GiB is reached;
+            // size = the tile's valid bytes), one per-lane offset for the whole
+            // kernel and the item's distance in the instruction's immediate.
+            // No address arithmetic per key and no clamp: a lane past the
+            // relation's end reads 0, and validity comes from cnt alone
+            constexpr uint32_t ESZ = COLS == 1 ? 8 : 16;
+            const uint32_t tu = __builtin_amdgcn_readfirstlane(t);
+            const uint32_t lo = tu * T;
+            const unsigned char* base = reinterpret_cast<const unsigned char*>(a.in_keys) + static_cast<size_t>(lo) * ESZ;
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<unsigned char*>(base), 0, static_cast<int>(min(static_cast<uint32_t>(T), a.n - lo) * ESZ), 0x00020000);
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+            u32x2 v[ITEMS];
+            uint32_t bvo = bvo0;
+            if (a.nt_load) {
+                __asm__ volatile("" : "+v"(bvo));
+#pragma unroll
+                for (int i = 0; i < ITEMS; i++) v[i] = __builtin_amdgcn_raw_buffer_load_b64(rs, bvo + static_cast<uint32_t>(i) * 64 * ESZ, 0, 2);
+            } else {
+                __asm__ volatile("" : "+v"(bvo));
+#pragma unroll
+                for (int i = 0; i < ITEMS; i++) v[i] = __builtin_amdgcn_raw_buffer_load_b64(rs, bvo + static_cast<uint32_t>(i) * 64 * ESZ, 0, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < ITEMS; i++) k[i] = static_cast<int64_t>(static_cast<uint64_t>(v[i].x) | (static_cast<uint64_t>(v[i].y) << 32));
+            return;
+        }
+#endif
         const uint32_t lo = t * T;
         if constexpr (COLS == 2) {
             // the pair clamped to the column's last two keys (host: n >= 2):
@@ -1343,8 +1427,8 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
         hot = a.hot_ctl[kHotCtlEntries] != 0 && a.hot_ctl[kHotCtlMass] >= a.hot_min_mass;
         if (hot)
             for (uint32_t i = tid; i < nb * kHotPer; i += BLOCK) {
-                hcode[i] = a.hot_code[i];
-                if constexpr (HOT == 1) hwt[i] = 0;
+                *hot_code(i) = a.hot_code[i];
+                if constexpr (HOT == 1) *hot_wt(hot_wt_off(i / kHotWays, i % kHotWays)) = 0;
             }
         if constexpr (BATCH != 0)
             if (tid == 0) tmp[21] = tmp[22] = 0;   // (tmp[20] is reset by every close before it is read)
@@ -1388,9 +1472,10 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             // PROF words here (thread 0's clocks): 0 front, 1 append, 2 protocol
             // and the wait at A (the other waves' fronts, protocols and spin
             // waits), 3 write-out, 4 sort stage, 5 batches, 7 tiles, 14
-            // iterations, 15 workgroups. The PROF forms are at 128 VGPRs and the
-            // XXH3 ones spill 2 VGPRs (12 B of scratch): the clocks are those of
-            // a slightly heavier kernel than the shipped one (124 / 126 VGPRs)
+            // iterations, 15 workgroups. The PROF forms are at 128 VGPRs and spill
+            // 2 (Murmur3) or 4 (XXH3) VGPRs, 12 / 20 B of scratch: the clocks are
+            // those of a slightly heavier kernel than the shipped one (127 / 128
+            // VGPRs, no scratch)
             auto biter = [&](auto kbc, auto cbc) -> bool {
                 constexpr int kb = decltype(kbc)::value, cb = decltype(cbc)::value;
                 uint32_t(&v0)[DPT] = cv0[cb];
@@ -1425,45 +1510,87 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                     else hash_all(F0{}, std::false_type{});
                     const uint32_t ahead = tile + KPF * slots;
                     load(key[kb], ahead < t_end ? ahead : tile);
-                    // every set read first, then the compares; a hot code adds 1
-                    // to its entry's weight (no return value) and is not kept
-                    uint32_t keep = 0;
-                    uint4 set[ITEMS];
-                    uint32_t e[ITEMS];
+                    // full: a whole tile, no validity compare anywhere in it (the
+                    // loads above stay outside the forms, as hash_all's)
+                    auto rest = [&](auto full) {
+                        // every set read first, then the compares; a hot code adds 1
+                        // to its entry's weight (no return value) and is not kept.
+                        // The kept predicates stay lane masks from the compares to
+                        // the ballots and the stores
+                        bool keep[ITEMS];
+                        uint64_t kb[ITEMS];   // their ballots
+                        hot_set_t set[ITEMS];
+                        uint32_t so[ITEMS];   // the set's byte offset
 #pragma unroll
-                    for (int i = 0; i < ITEMS; i++) {
-                        keep |= (pipe_elem<COLS>(wbase, lane, i) < cnt ? 1u : 0u) << i;
-                        e[i] = dig[i] * kHotPer + static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 63) * kHotWays;
-                        set[i] = *reinterpret_cast<const uint4*>(hcode + e[i]);
-                    }
+                        for (int i = 0; i < ITEMS; i++) {
+                            so[i] = hot_set_off(dig[i] * kHotSub + static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 63));
+                            set[i] = *reinterpret_cast<const hot_set_t*>(hbase + so[i]);
+                        }
+                        // (the whole set is used here, to the compiler's eyes: the read
+                        // stays one 16-B read, none of its words sunk behind a branch.
+                        // An empty statement: no instruction and no wait of its own)
+                        if constexpr (PHJ_P1F_SET128 != 0) {
 #pragma unroll
-                    for (int i = 0; i < ITEMS; i++) {
-                        const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
-                        const bool m0 = set[i].x == lo && set[i].y == hi, m1 = set[i].z == lo && set[i].w == hi;
-                        const bool m = (m0 || m1) && ((keep >> i) & 1u) != 0;
-                        if (m) atomicAdd(&hwt[e[i] + (m0 ? 0u : 1u)], 1u);
-                        keep &= ~((m ? 1u : 0u) << i);
-                    }
-                    ptick(0);
-                    // append: the wave's kept codes take consecutive indices, one LDS atomic per wave
-                    uint32_t off[ITEMS], wtot = 0;
+                            for (int i = 0; i < ITEMS; i++) __asm__ volatile("" ::"v"(set[i]));
+                        }
 #pragma unroll
-                    for (int i = 0; i < ITEMS; i++) {
-                        const uint64_t b = __ballot(((keep >> i) & 1u) != 0);
-                        off[i] = wtot + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u));
-                        wtot += static_cast<uint32_t>(__popcll(b));
-                    }
-                    uint32_t wbase_g = 0;
-                    if (lane == 0) wbase_g = atomicAdd(&tmp[21 + cb], wtot);
-                    wbase_g = __builtin_amdgcn_readfirstlane(wbase_g) - wprev[cb] + gtot;
+                        for (int i = 0; i < ITEMS; i++) {
+                            const bool valid = decltype(full)::value || pipe_elem<COLS>(wbase, lane, i) < cnt;
+                            const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
+                            const bool x0 = set[i].x == lo, y0 = set[i].y == hi, x1 = set[i].z == lo, y1 = set[i].w == hi;
+                            const bool m0 = x0 && y0, m1 = x1 && y1;
+                            const bool m = (m0 || m1) && valid;
+                            // (the kept codes' ballot from the ballots of the four plain
+                            // compares, each the compare's own lane mask: the ballot of a
+                            // combined predicate is rebuilt through a VGPR, two VALU more)
+                            if constexpr (PHJ_P1F_CMPBALLOT != 0) {
+                                const uint64_t bm = (__builtin_amdgcn_ballot_w64(x0) & __builtin_amdgcn_ballot_w64(y0)) |
+                                                    (__builtin_amdgcn_ballot_w64(x1) & __builtin_amdgcn_ballot_w64(y1));
+                                kb[i] = ~bm & __builtin_amdgcn_ballot_w64(valid);
+                            }
+                            if (m) {
+                                if constexpr (PHJ_P1F_WTADDR != 0) atomicAdd(hot_wt(so[i] + (m0 ? kHotWays * 8 : kHotWays * 8 + 4)), 1u);
+                                else atomicAdd(hot_wt(nb * kHotPer * 8 + (so[i] >> 1) + (m0 ? 0u : 4u)), 1u);
+                            }
+                            keep[i] = valid && !m;
+                        }
+                        ptick(0);
+                        // append: the wave's kept codes take consecutive indices, one LDS atomic per wave
+                        // (item i's index in the wave = pre[i], wave-uniform, + mb[i])
+                        uint32_t mb[ITEMS], pre[ITEMS], wtot = 0;
 #pragma unroll
-                    for (int i = 0; i < ITEMS; i++) {
-                        gi[i] = wbase_g + off[i];
-                        const bool k = ((keep >> i) & 1u) != 0, now = k && gi[i] - gsort < static_cast<uint32_t>(T);
-                        if (now) sbuf[gi[i] & (2 * T - 1)] = code[i];
-                        held |= (k && !now ? 1u : 0u) << i;
-                    }
-                    ptick(1);
+                        for (int i = 0; i < ITEMS; i++) {
+                            const uint64_t b = PHJ_P1F_CMPBALLOT != 0 ? kb[i] : __builtin_amdgcn_ballot_w64(keep[i]);
+                            mb[i] = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u));
+                            pre[i] = wtot;
+                            wtot += static_cast<uint32_t>(__popcll(b));
+                        }
+                        uint32_t wbase_g = 0;
+                        if (lane == 0) wbase_g = atomicAdd(&tmp[21 + cb], wtot);
+                        wbase_g = __builtin_amdgcn_readfirstlane(wbase_g) - wprev[cb] + gtot;
+                        // (wave-uniform, and no barrier inside: wbase_g >= gsort, so the
+                        // wave's last index is inside the batch being filled or past it.
+                        // gsort is a multiple of T: inside the batch the wave's slots do
+                        // not wrap around the ring, and a slot's address is one shift-add
+                        // onto a scalar)
+                        if (PHJ_P1F_WAVEFAST != 0 && wbase_g + wtot - gsort <= static_cast<uint32_t>(T)) {
+                            int64_t* const wslot = sbuf + (wbase_g & (2 * T - 1));
+#pragma unroll
+                            for (int i = 0; i < ITEMS; i++)
+                                if (keep[i]) (wslot + pre[i])[mb[i]] = code[i];
+                        } else {
+#pragma unroll
+                            for (int i = 0; i < ITEMS; i++) {
+                                gi[i] = wbase_g + pre[i] + mb[i];
+                                const bool now = keep[i] && gi[i] - gsort < static_cast<uint32_t>(T);
+                                if (now) sbuf[gi[i] & (2 * T - 1)] = code[i];
+                                held |= (keep[i] && !now ? 1u : 0u) << i;
+                            }
+                        }
+                        ptick(1);
+                    };
+                    if (PHJ_P1F_FULL != 0 && cnt == static_cast<uint32_t>(T)) rest(std::true_type{});
+                    else rest(std::false_type{});
                 }
                 const uint32_t pp = (nbat - 1) & 1u;   // the pending batch's half, row and words
                 if (pend) {
@@ -1651,7 +1778,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             }
             // (every weight add is before barrier A of the drain's first iteration)
             for (uint32_t i = tid; i < nb * kHotPer; i += BLOCK) {
-                const uint32_t w = hwt[i];
+                const uint32_t w = *hot_wt(hot_wt_off(i / kHotWays, i % kHotWays));
                 if (w) atomicAdd(&a.hot_w[i], static_cast<unsigned long long>(w));
             }
             return;
@@ -1716,15 +1843,15 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                     uint32_t e[ITEMS];
 #pragma unroll
                     for (int i = 0; i < ITEMS; i++) {
-                        e[i] = dig[i] * kHotPer + static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 63) * kHotWays;
-                        set[i] = *reinterpret_cast<const uint4*>(hcode + e[i]);
+                        e[i] = dig[i] * kHotSub + static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 63);
+                        set[i] = *reinterpret_cast<const uint4*>(hbase + hot_set_off(e[i]));
                     }
 #pragma unroll
                     for (int i = 0; i < ITEMS; i++) {
                         const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
                         const bool m0 = set[i].x == lo && set[i].y == hi, m1 = set[i].z == lo && set[i].w == hi;
                         const bool m = (m0 || m1) && ((keep >> i) & 1u) != 0;
-                        hew[i] = e[i] + (m0 ? 0u : 1u);
+                        hew[i] = hot_wt_off(e[i], m0 ? 0u : 1u);
                         hm |= (m ? 1u : 0u) << i;
                     }
                     if constexpr (HOT == 1) keep &= ~hm;
@@ -1739,7 +1866,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
                     const bool m = ((hm >> i) & 1u) != 0, k = ((keep >> i) & 1u) != 0;
-                    rank[i] = atomicAdd(m ? &hwt[hew[i]] : k ? &crow[dig[i]] : &hown[tid], m || k ? 1u : 0u);
+                    rank[i] = atomicAdd(m ? hot_wt(hew[i]) : k ? &crow[dig[i]] : &hown[tid], m || k ? 1u : 0u);
                 }
 #else
                 // the weight add (a lane without a match adds 0 to a word of its
@@ -1748,7 +1875,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
 #pragma unroll
                     for (int i = 0; i < ITEMS; i++) {
                         const bool m = ((hm >> i) & 1u) != 0;
-                        atomicAdd(m ? &hwt[hew[i]] : &hown[tid], m ? 1u : 0u);
+                        atomicAdd(m ? hot_wt(hew[i]) : &hown[tid], m ? 1u : 0u);
                     }
                 }
 #pragma unroll
@@ -1960,7 +2087,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
         // (every weight add is before a barrier of the drained iteration)
         if (hot)
             for (uint32_t i = tid; i < nb * kHotPer; i += BLOCK) {
-                const uint32_t w = hwt[i];
+                const uint32_t w = *hot_wt(hot_wt_off(i / kHotWays, i % kHotWays));
                 if (w) atomicAdd(&a.hot_w[i], static_cast<unsigned long long>(w));
             }
     }
