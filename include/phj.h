@@ -677,6 +677,54 @@ int phj_index_lookup(phj_ctx *ctx, const phj_index *index, const int64_t *dev_ke
  * ctx does not hold (destroyed before, or another context's) is ignored. */
 void phj_index_destroy(phj_ctx *ctx, phj_index *index);
 
+/* ---- ordinals on the key index: a dense id per distinct key ----
+ * phj_index_build_ex(flags = PHJ_INDEX_ORDINALS) builds the index above and
+ * gives every distinct key its ordinal: the number of distinct build keys whose
+ * first row is lower than this key's first row. That is first-appearance
+ * order, 0 .. distinct-1: pandas.factorize of the build key column, or the
+ * inverse of torch.unique in the order keys first appear. flags == 0 is
+ * phj_index_build exactly; any other bit gives PHJ_ERR_INVALID. The ordinal
+ * build adds one timer, `index.ordinals`, and its rules are phj_index_build's
+ * (single-device contexts, fewer than 2^30 build rows, an empty build side
+ * gives a valid index with distinct == 0).
+ *
+ *  - phj_index_uniques: *dev_first_rows (int64, the index's own device memory,
+ *    *n == distinct entries, strictly ascending, valid as long as the index) is
+ *    the first row of the key with ordinal j: uniques =
+ *    keys.index_select(0, first_rows), and uniques[encode(keys)] == keys.
+ *    phj_index_info.table_bytes counts the array.
+ *  - phj_index_encode has phj_index_lookup's contract word for word (enqueue
+ *    only on the context's stream; no synchronise, event, allocation or copy
+ *    back; key_stride 1 or 2; 8-byte aligned pointers, out_found at any
+ *    alignment; exactly [0, n) of each output written; n == 0 launches
+ *    nothing) and writes out_codes[i] = the key's ordinal, or PHJ_NO_ROW for a
+ *    key the index does not hold. The bucket holds the ordinal, so a key that
+ *    settles at home reads one 64-byte line. dev_keys may be the column the
+ *    index was built from (it is only read): that is factorize.
+ *  - phj_index_lookup on an ordinal index returns rows as on a plain one, at
+ *    the price of one dependent read of first_rows per found key.
+ *  - phj_index_accumulate, enqueue-only like encode: for every key the index
+ *    holds, dev_counts[ordinal] += 1 and, when dev_values and dev_sums are
+ *    given (both or neither, else PHJ_ERR_INVALID), dev_sums[ordinal] +=
+ *    dev_values[i * value_stride] modulo 2^64 (value_stride 1 or 2), so the
+ *    result does not depend on the order of arrival. Absent keys are skipped
+ *    and added to *dev_missing_count (optional). The caller owns and zeroes
+ *    the accumulators (distinct entries each, 8-byte aligned); successive
+ *    batches add up. dev_counts is required unless n == 0. Nothing else is
+ *    written.
+ *  - On an index built without the flag, uniques, encode and accumulate return
+ *    PHJ_ERR_STATE ("index built without ordinals") and launch nothing. The
+ *    index must belong to ctx. */
+#define PHJ_INDEX_ORDINALS 0x1
+int phj_index_build_ex(phj_ctx *ctx, const phj_join_params *p, uint32_t flags, phj_index **out, phj_join_result *r);
+int phj_index_flags_get(const phj_index *index, uint32_t *flags);
+int phj_index_uniques(phj_ctx *ctx, const phj_index *index, const int64_t **dev_first_rows, uint64_t *n);
+int phj_index_encode(phj_ctx *ctx, const phj_index *index, const int64_t *dev_keys, uint32_t key_stride, uint64_t n,
+                     int64_t *out_codes, uint8_t *out_found, unsigned long long *dev_found_count);
+int phj_index_accumulate(phj_ctx *ctx, const phj_index *index, const int64_t *dev_keys, uint32_t key_stride,
+                         const int64_t *dev_values, uint32_t value_stride, uint64_t n, unsigned long long *dev_counts,
+                         int64_t *dev_sums, unsigned long long *dev_missing_count);
+
 /* ---- building blocks (multi-GPU: range-sharded relations, RCCL exchange) ---- */
 /* Radix-partition the bound relation of `side`; fills `out` with ctx-owned views.
  * Asynchronous on the ctx stream (order later work on the same stream). */

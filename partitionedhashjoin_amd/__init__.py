@@ -452,15 +452,21 @@ class Context:
                     o[0].close()
         return r, cnt, masks[0], masks[1]
 
-    def build_index(self, params: JoinParams) -> "Index":
+    def build_index(self, params: JoinParams, ordinals: bool = False) -> "Index":
         """phj_index_build: a retained key index over the build side as bound
         (keys only; any binding, a key column alone included): each distinct
         key once with the lowest row that carries it. The index owns its
         memory and outlives later joins and rebinds of this context; close it
         with Index.close() (closing the context closes its indexes). The
-        build's JoinResult is Index.result (matches = the distinct keys)."""
+        build's JoinResult is Index.result (matches = the distinct keys).
+        ordinals=True (phj_index_build_ex, PHJ_INDEX_ORDINALS) also numbers the
+        distinct keys 0 .. distinct-1 in first-appearance order: Index.encode,
+        Index.accumulate and Index.first_rows need it."""
         h, r = C.c_void_p(), JoinResult()
-        self._check(self._L.phj_index_build(self._h, C.byref(params), C.byref(h), C.byref(r)))
+        if ordinals:
+            self._check(self._L.phj_index_build_ex(self._h, C.byref(params), _capi.INDEX_ORDINALS, C.byref(h), C.byref(r)))
+        else:
+            self._check(self._L.phj_index_build(self._h, C.byref(params), C.byref(h), C.byref(r)))
         ix = Index(self, h, r)
         if not hasattr(self, "_indexes"):
             self._indexes = []
@@ -615,6 +621,105 @@ class Index:
             rows = np.ascontiguousarray(donor.download(SIDE_PROBE)[:, 1])
             found = np.ascontiguousarray(donor.download(SIDE_BUILD)[:, 0]).view(np.uint8)[:n].astype(bool)
         return rows, found
+
+    @property
+    def ordinals(self) -> bool:
+        """Whether the index was built with ordinals (phj_index_flags_get)."""
+        f = C.c_uint32(0)
+        rc = self._ctx._L.phj_index_flags_get(self._handle(), C.byref(f))
+        if rc != 0:
+            raise PhjError(rc, "phj_index_flags_get failed")
+        return bool(f.value & _capi.INDEX_ORDINALS)
+
+    def first_rows_ptr(self) -> tuple:
+        """phj_index_uniques: (device address, n) of first_rows, int64, n ==
+        distinct, ascending: first_rows[j] is the first build row of the key
+        with ordinal j. The index's memory; the address is 0 when n is 0."""
+        c = self._ctx
+        p, n = C.c_void_p(), C.c_uint64(0)
+        c._check(c._L.phj_index_uniques(c._h, self._handle(), C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def first_rows(self) -> np.ndarray:
+        """A host copy of first_rows: keys[first_rows()] are the distinct keys
+        in ordinal order."""
+        ptr, n = self.first_rows_ptr()
+        if n == 0:
+            return np.zeros(0, dtype=np.int64)
+        c = self._ctx
+        c.synchronize()
+        with Context(c.device) as donor:   # a device-to-host copy through a borrowed key column
+            donor.bind_columns(SIDE_PROBE, ptr, None, n)
+            return np.ascontiguousarray(donor.download(SIDE_PROBE)[:, 0])
+
+    def encode(self, keys_ptr: int, n: int, codes_ptr: int, found_ptr: int | None = None,
+               count_ptr: int | None = None, key_stride: int = 1) -> None:
+        """phj_index_encode on device pointers, enqueue-only like lookup():
+        codes[i] = the ordinal of keys[i * key_stride], or NO_ROW."""
+        c = self._ctx
+        c._check(c._L.phj_index_encode(c._h, self._handle(), C.c_void_p(keys_ptr or 0), key_stride, n,
+                                       C.c_void_p(codes_ptr or 0), C.c_void_p(found_ptr or 0),
+                                       C.c_void_p(count_ptr or 0)))
+
+    def accumulate(self, keys_ptr: int, n: int, counts_ptr: int, values_ptr: int | None = None,
+                   sums_ptr: int | None = None, missing_ptr: int | None = None, key_stride: int = 1,
+                   value_stride: int = 1) -> None:
+        """phj_index_accumulate on device pointers, enqueue-only: counts[ordinal]
+        += 1 and sums[ordinal] += values[i * value_stride] (modulo 2^64) for
+        every key the index holds; absent keys are added to the uint64 at
+        missing_ptr. The caller zeroes the accumulators (distinct entries)."""
+        c = self._ctx
+        c._check(c._L.phj_index_accumulate(c._h, self._handle(), C.c_void_p(keys_ptr or 0), key_stride,
+                                           C.c_void_p(values_ptr or 0), value_stride, n, C.c_void_p(counts_ptr or 0),
+                                           C.c_void_p(sums_ptr or 0), C.c_void_p(missing_ptr or 0)))
+
+    def encode_host(self, keys):
+        """(codes, found) for a host array of int64 keys (lookup_host's shape)."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        assert keys.ndim == 1
+        n = keys.shape[0]
+        if n == 0:
+            self.first_rows_ptr()   # (the state checks of an encode)
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=bool)
+        with Context(self._ctx.device) as donor:
+            donor.upload_columns(SIDE_PROBE, keys, np.zeros(n, dtype=np.int64))
+            donor.upload_columns(SIDE_BUILD, np.zeros((n + 7) // 8, dtype=np.int64))
+            kp, cp, _ = donor.columns_ptr(SIDE_PROBE)
+            fp = donor.columns_ptr(SIDE_BUILD)[0]
+            self.encode(kp, n, cp, fp)
+            self._ctx.synchronize()
+            codes = np.ascontiguousarray(donor.download(SIDE_PROBE)[:, 1])
+            found = np.ascontiguousarray(donor.download(SIDE_BUILD)[:, 0]).view(np.uint8)[:n].astype(bool)
+        return codes, found
+
+    def accumulate_host(self, keys, values=None):
+        """(counts, sums, missing) of one batch of host keys (and int64
+        values): counts uint64 and sums int64 with `distinct` entries, sums
+        None without values, missing the number of keys the index lacks."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        assert keys.ndim == 1
+        n = keys.shape[0]
+        d = self.first_rows_ptr()[1]
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.int64)
+            assert values.shape == keys.shape
+        counts = np.zeros(d, dtype=np.uint64)
+        sums = np.zeros(d, dtype=np.int64) if values is not None else None
+        if n == 0:
+            return counts, sums, 0
+        with Context(self._ctx.device) as donor:
+            donor.upload_columns(SIDE_PROBE, keys, values)
+            # the accumulators and the missing counter, zeroed: {counts | missing}, {sums}
+            donor.upload_columns(SIDE_BUILD, np.zeros(d + 1, dtype=np.int64), np.zeros(d + 1, dtype=np.int64))
+            kp, vp, _ = donor.columns_ptr(SIDE_PROBE)
+            ap, sp, _ = donor.columns_ptr(SIDE_BUILD)
+            self.accumulate(kp, n, ap, vp if values is not None else None, sp if values is not None else None, ap + 8 * d)
+            self._ctx.synchronize()
+            acc = donor.download(SIDE_BUILD)
+        counts = np.ascontiguousarray(acc[:d, 0]).view(np.uint64)
+        if values is not None:
+            sums = np.ascontiguousarray(acc[:d, 1])
+        return counts, sums, int(np.uint64(acc[d, 0]))
 
     def close(self):
         c = self._ctx

@@ -47,11 +47,13 @@ EXPORTED = [
     "phj_join_indices", "phj_joined_indices", "phj_joined_indices_download", "phj_gather_column",
     "phj_join_member",
     "phj_index_build", "phj_index_info_get", "phj_index_lookup", "phj_index_destroy",
+    "phj_index_build_ex", "phj_index_flags_get", "phj_index_uniques", "phj_index_encode", "phj_index_accumulate",
 ]
 ABI_VERSION = 2
 CTX_EXCHANGE = 0x1   # phj_ctx_create_ex: the multi-GPU path on one device (RCCL world of one)
 CTX_LOCAL = 0x2      # ... exchange by device copies; devices may repeat (rehearsal on one GPU)
 UNIQUE_ID_BYTES = 128
+INDEX_ORDINALS = 0x1  # phj_index_build_ex: a dense id per distinct key (encode, accumulate, uniques)
 PATH_NO_PARTITIONING, PATH_LDS_JOIN, PATH_CODE_TABLES, PATH_PARTITIONED = 0, 1, 2, 3   # phj_join_path
 # phj_join_rows: the row classes and the join kinds they make
 ROWS_PAIRS, ROWS_PROBE_ONLY, ROWS_BUILD_ONLY = 0x1, 0x2, 0x4
@@ -244,6 +246,11 @@ def load():
         "phj_index_info_get": (i, [P, C.POINTER(IndexInfo)]),
         "phj_index_lookup": (i, [P, P, P, C.c_uint32, u64, P, P, P]),
         "phj_index_destroy": (None, [P, P]),
+        "phj_index_build_ex": (i, [P, C.POINTER(JoinParams), C.c_uint32, C.POINTER(P), C.POINTER(JoinResult)]),
+        "phj_index_flags_get": (i, [P, C.POINTER(C.c_uint32)]),
+        "phj_index_uniques": (i, [P, P, C.POINTER(P), C.POINTER(u64)]),
+        "phj_index_encode": (i, [P, P, P, C.c_uint32, u64, P, P, P]),
+        "phj_index_accumulate": (i, [P, P, P, C.c_uint32, P, C.c_uint32, u64, P, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name, None)

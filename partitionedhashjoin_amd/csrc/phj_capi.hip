@@ -58,6 +58,7 @@
 #include "phj_inner.h"
 #include "phj_outer.h"
 #include "phj_index.h"
+#include "phj_ordinal.h"
 #include "phj_agg.h"
 #include "phj_mat.h"
 #include "phj_partition.h"
@@ -289,6 +290,10 @@ struct phj_index {
     uint64_t seed = 0;
     uint64_t rows = 0, distinct = 0;
     uint32_t max_wgs = 1;   // workgroups that fill the chip once at the lookup's occupancy
+    // PHJ_INDEX_ORDINALS (phj_ordinal.h): the slots hold ordinals; first_rows[ordinal] = the key's first row
+    uint32_t flags = 0;
+    int64_t* first_rows = nullptr;   // `distinct` entries, the index's own memory (counted in bytes)
+    uint32_t acc_wgs = 1;            // max_wgs of k_ix_accumulate
 };
 
 namespace {
@@ -2335,13 +2340,15 @@ int index_geometry(phj_ctx* c, uint64_t rows, double table_ratio, NPHome& g) {
     return PHJ_OK;
 }
 
-int index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_result* r) {
+int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index** out, phj_join_result* r) {
     const char* what = "phj_index_build";
     if (!c || !out || !r) return PHJ_ERR_INVALID;
     *out = nullptr;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
     (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
+    if (flags & ~static_cast<uint32_t>(PHJ_INDEX_ORDINALS)) return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": unknown flags");
+    const bool ordinals = (flags & PHJ_INDEX_ORDINALS) != 0;
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
     if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3) return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
@@ -2363,14 +2370,19 @@ int index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_
     c->ks = c->stream;
     reset_timers(c);
     const uint32_t nb = g.nb;
+    // ordinals: one bit per build row in 32-bit words, rounded to 16 B so that the rank array behind it scans vectorised
+    const uint64_t ord_words = ((R.n + 31) / 32 + 3) & ~3ull;
     if (R.n > 0) {   // the workspace first: a grow synchronises, and nothing of the index exists yet
         PHJ_TRY(ensure(c, c->count, 32));
-        PHJ_TRY(ensure(c, c->np_ovf, R.n * 16));
+        // (ordinals: the bitmap and the rank array take the overflow list's place once that pass is done)
+        PHJ_TRY(ensure(c, c->np_ovf, std::max<uint64_t>(R.n * 16, ordinals ? 2 * ord_words * 4 : 0)));
         PHJ_TRY(ensure(c, c->np_ovfb, R.n * 4));
         PHJ_TRY(ensure(c, c->np_ovfn, 4));
+        if (ordinals) PHJ_TRY(ensure(c, c->scan_partials, (ord_words + kScanBlockElems - 1) / kScanBlockElems * 4));
     }
     phj_index* ix = new phj_index();
     ix->owner = c;
+    ix->flags = flags;
     ix->g = g;
     ix->hk = p->hash;
     ix->seed = p->hash_seed;
@@ -2378,6 +2390,7 @@ int index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_
     ix->bytes = static_cast<size_t>(nb) * sizeof(IxBucket);
     auto fail = [&](int rc) {
         if (ix->tab) (void)hipFree(ix->tab);
+        if (ix->first_rows) (void)hipFree(ix->first_rows);
         delete ix;
         return rc;
     };
@@ -2406,6 +2419,14 @@ int index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_
     int per_cu = occupancy(kfn, 256, 0);
     if (per_cu < 1) per_cu = 4;
     ix->max_wgs = static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(std::max(1, c->num_cus));
+    if (ordinals) {
+        const void* afn = with_hash(p->hash, [&](auto h) {
+            return reinterpret_cast<const void*>(&k_ix_accumulate<decltype(h)::value, 1>);
+        });
+        per_cu = occupancy(afn, 256, 0);
+        if (per_cu < 1) per_cu = 4;
+        ix->acc_wgs = static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(std::max(1, c->num_cus));
+    }
     if (R.n == 0) {   // a valid index over nothing: every bucket empty, every lookup misses
         PHJ_IX(hip(hipMemsetAsync(ix->tab, 0, ix->bytes, c->ks), "hipMemsetAsync"));
         PHJ_IX(hip(hipStreamSynchronize(c->ks), "hipStreamSynchronize"));
@@ -2449,11 +2470,51 @@ int index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_
         PHJ_IX(hip(hipGetLastError(), "launch k_ix_build_overflow"));
     }
     PHJ_IX(timer_end(c));
-    PHJ_IX(mark(c, &e1));
+    if (!ordinals) PHJ_IX(mark(c, &e1));
     unsigned long long h[2] = {0, 0};   // {distinct codes, the overflow pass gave up on a tuple}
     PHJ_IX(hip(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->ks), "hipMemcpyAsync"));
     PHJ_IX(hip(hipStreamSynchronize(c->ks), "hipStreamSynchronize"));
     if (h[1]) return fail(set_err(c, PHJ_ERR_STATE, std::string(what) + ": the table had no room for a key"));
+    if (ordinals) {   // first_rows has `distinct` entries: allocated once that is known, then the four passes
+        c->since_ev++;   // (the copy back and the wait lie between the two timers: no shared boundary event)
+        const uint64_t distinct = h[0];
+        const size_t fbytes = static_cast<size_t>(distinct) * sizeof(int64_t);
+        void* mem = nullptr;
+        const hipError_t e = hipMalloc(&mem, fbytes);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(set_err(c, PHJ_ERR_NOMEM, "hipMalloc(" + std::to_string(fbytes) + "): " + hipGetErrorString(e)));
+        }
+        ix->first_rows = static_cast<int64_t*>(mem);
+        ix->bytes += fbytes;
+        if (c->poison >= 0) PHJ_IX(hip(hipMemsetAsync(ix->first_rows, c->poison, fbytes, c->ks), "hipMemsetAsync"));
+        const uint32_t rows = static_cast<uint32_t>(R.n), words = static_cast<uint32_t>(ord_words);
+        uint32_t* bitmap = static_cast<uint32_t*>(c->np_ovf.p);   // (the overflow pass is done with it)
+        uint32_t* rank = bitmap + words;
+        // algorithmic bytes: the row words of every bucket read twice and written once (a 32-B half line each
+        // time), the bitmap cleared, written, and read three times, the rank written, scanned (read twice,
+        // written once) and read twice, first_rows written
+        PHJ_IX(timer_begin(c, "index.ordinals", static_cast<uint64_t>(nb) * 96 + static_cast<uint64_t>(words) * (20 + 24) + fbytes));
+        PHJ_IX(hip(hipMemsetAsync(bitmap, 0, static_cast<size_t>(words) * 4, c->ks), "hipMemsetAsync"));
+        const uint32_t sgrid = static_cast<uint32_t>((static_cast<uint64_t>(nb) * 8 + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_ix_ord_mark, dim3(sgrid), dim3(kBlock), 0, c->ks, ix->tab, nb, rows, bitmap);
+        c->since_ev++;
+        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_mark"));
+        hipLaunchKernelGGL(k_ix_ord_popc, dim3((words + kBlock - 1) / kBlock), dim3(kBlock), 0, c->ks, bitmap, words, rank);
+        c->since_ev++;
+        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_popc"));
+        PHJ_IX(scan_u32(c, rank, words, 1, words));
+        hipLaunchKernelGGL(k_ix_ord_first, dim3((rows + kBlock - 1) / kBlock), dim3(kBlock), 0, c->ks, bitmap, rank, rows,
+                           ix->first_rows, distinct);
+        c->since_ev++;
+        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_first"));
+        hipLaunchKernelGGL(k_ix_ord_apply, dim3(sgrid), dim3(kBlock), 0, c->ks, ix->tab, nb, rows, bitmap, rank);
+        c->since_ev++;
+        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_apply"));
+        PHJ_IX(timer_end(c));
+        PHJ_IX(mark(c, &e1));
+        PHJ_IX(hip(hipStreamSynchronize(c->ks), "hipStreamSynchronize"));
+    }
 #undef PHJ_IX
     ix->distinct = h[0];
     r->matches = h[0];
@@ -2472,12 +2533,14 @@ int index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_
 
 // phj_index_lookup: one launch on the context's stream and nothing else: no
 // event, no allocation, no copy back, no synchronisation.
+// codes: phj_index_encode, the ordinals of an ordinal index in place of rows.
 int index_lookup(phj_ctx* c, const phj_index* ix, const int64_t* keys, uint32_t key_stride, uint64_t n, int64_t* out_rows,
-                 uint8_t* out_found, unsigned long long* dev_found_count) {
-    const char* what = "phj_index_lookup";
+                 uint8_t* out_found, unsigned long long* dev_found_count, bool codes = false) {
+    const char* what = codes ? "phj_index_encode" : "phj_index_lookup";
     if (!c || !ix) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
     if (ix->owner != c) return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": the index belongs to another context");
+    if (codes && !(ix->flags & PHJ_INDEX_ORDINALS)) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": index built without ordinals");
     if (key_stride != 1 && key_stride != 2)
         return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": key_stride must be 1 (a key column) or 2 (the ids of tuples)");
     if (n == 0) return PHJ_OK;
@@ -2496,16 +2559,73 @@ int index_lookup(phj_ctx* c, const phj_index* ix, const int64_t* keys, uint32_t 
     a.rows = out_rows;
     a.found = out_found;
     a.count = dev_found_count;
+    a.first = ix->first_rows;
+    const bool ord = (ix->flags & PHJ_INDEX_ORDINALS) != 0;
     const void* kfn = with_hash(ix->hk, [&](auto h) {
         constexpr int HK = decltype(h)::value;
-        return key_stride == 1 ? reinterpret_cast<const void*>(&k_ix_lookup<HK, 1>)
-                               : reinterpret_cast<const void*>(&k_ix_lookup<HK, 2>);
+        auto pick = [&](auto m) {
+            constexpr IxMode M = decltype(m)::value;
+            return key_stride == 1 ? reinterpret_cast<const void*>(&k_ix_lookup<HK, 1, M>)
+                                   : reinterpret_cast<const void*>(&k_ix_lookup<HK, 2, M>);
+        };
+        if (!ord) return pick(std::integral_constant<IxMode, IxMode::Rows>{});
+        if (codes) return pick(std::integral_constant<IxMode, IxMode::Codes>{});
+        return pick(std::integral_constant<IxMode, IxMode::RowsVia>{});
     });
     const uint64_t per = 256ull * kIxItems;
     const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((n + per - 1) / per, ix->max_wgs)));
     void* kargs[] = {&a};
     PHJ_HIP(c, hipLaunchKernel(kfn, dim3(grid), dim3(256), kargs, 0, c->stream));
     PHJ_LAUNCHED(c, "k_ix_lookup");
+    return PHJ_OK;
+}
+
+// phj_index_accumulate: enqueue-only like the lookup. One launch per 2^31 keys
+// (k_ix_accumulate's cache counts in 32 bits between its flushes).
+int index_accumulate(phj_ctx* c, const phj_index* ix, const int64_t* keys, uint32_t key_stride, const int64_t* values,
+                     uint32_t value_stride, uint64_t n, unsigned long long* counts, int64_t* sums,
+                     unsigned long long* missing) {
+    const char* what = "phj_index_accumulate";
+    if (!c || !ix) return PHJ_ERR_INVALID;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
+    if (ix->owner != c) return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": the index belongs to another context");
+    if (!(ix->flags & PHJ_INDEX_ORDINALS)) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": index built without ordinals");
+    if (key_stride != 1 && key_stride != 2)
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": key_stride must be 1 (a key column) or 2 (the ids of tuples)");
+    if ((values == nullptr) != (sums == nullptr))
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": dev_values and dev_sums go together");
+    if (values && value_stride != 1 && value_stride != 2)
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": value_stride must be 1 or 2");
+    if (n == 0) return PHJ_OK;
+    if (!keys || !counts) return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": null keys or dev_counts");
+    if ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(values) | reinterpret_cast<uintptr_t>(counts) |
+         reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(missing)) & 7)
+        return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": every pointer needs 8-byte alignment");
+    (void)hipGetLastError();
+    PHJ_HIP(c, hipSetDevice(c->device));
+    const void* kfn = with_hash(ix->hk, [&](auto h) {
+        constexpr int HK = decltype(h)::value;
+        return key_stride == 1 ? reinterpret_cast<const void*>(&k_ix_accumulate<HK, 1>)
+                               : reinterpret_cast<const void*>(&k_ix_accumulate<HK, 2>);
+    });
+    const uint64_t per = 256ull * kIxItems;
+    for (uint64_t off = 0; off < n; off += kIxAccLaunchKeys) {
+        IxAccArgs a{};
+        a.n = std::min<uint64_t>(kIxAccLaunchKeys, n - off);
+        a.keys = keys + off * key_stride;
+        a.tab = ix->tab;
+        a.g = ix->g;
+        a.seed = ix->seed;
+        a.values = values ? values + off * value_stride : nullptr;
+        a.vstride = value_stride;
+        a.counts = counts;
+        a.sums = reinterpret_cast<unsigned long long*>(sums);
+        a.missing = missing;
+        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((a.n + per - 1) / per, ix->acc_wgs)));
+        void* kargs[] = {&a};
+        PHJ_HIP(c, hipLaunchKernel(kfn, dim3(grid), dim3(256), kargs, 0, c->stream));
+        PHJ_LAUNCHED(c, "k_ix_accumulate");
+    }
     return PHJ_OK;
 }
 
@@ -3702,6 +3822,7 @@ void phj_ctx_destroy(phj_ctx* c) {
         free_buf(*b);
     for (phj_index* ix : c->indexes) {
         if (ix->tab) (void)hipFree(ix->tab);
+        if (ix->first_rows) (void)hipFree(ix->first_rows);
         delete ix;
     }
     for (hipEvent_t e : c->evpool) (void)hipEventDestroy(e);
@@ -4611,7 +4732,40 @@ int phj_join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_
 static_assert(sizeof(phj_index_info) == 40, "phj_index_info layout");
 
 int phj_index_build(phj_ctx* c, const phj_join_params* p, phj_index** out, phj_join_result* r) {
-    return index_build(c, p, out, r);
+    return index_build(c, p, 0, out, r);
+}
+
+int phj_index_build_ex(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index** out, phj_join_result* r) {
+    return index_build(c, p, flags, out, r);
+}
+
+int phj_index_flags_get(const phj_index* ix, uint32_t* flags) {
+    if (!ix || !flags) return PHJ_ERR_INVALID;
+    *flags = ix->flags;
+    return PHJ_OK;
+}
+
+int phj_index_uniques(phj_ctx* c, const phj_index* ix, const int64_t** dev_first_rows, uint64_t* n) {
+    if (!c || !ix || !dev_first_rows || !n) return PHJ_ERR_INVALID;
+    *dev_first_rows = nullptr;
+    *n = 0;
+    if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_index_uniques: single-device contexts only");
+    if (ix->owner != c) return set_err(c, PHJ_ERR_INVALID, "phj_index_uniques: the index belongs to another context");
+    if (!(ix->flags & PHJ_INDEX_ORDINALS)) return set_err(c, PHJ_ERR_STATE, "phj_index_uniques: index built without ordinals");
+    *dev_first_rows = ix->distinct ? ix->first_rows : nullptr;
+    *n = ix->distinct;
+    return PHJ_OK;
+}
+
+int phj_index_encode(phj_ctx* c, const phj_index* ix, const int64_t* dev_keys, uint32_t key_stride, uint64_t n,
+                     int64_t* out_codes, uint8_t* out_found, unsigned long long* dev_found_count) {
+    return index_lookup(c, ix, dev_keys, key_stride, n, out_codes, out_found, dev_found_count, true);
+}
+
+int phj_index_accumulate(phj_ctx* c, const phj_index* ix, const int64_t* dev_keys, uint32_t key_stride,
+                         const int64_t* dev_values, uint32_t value_stride, uint64_t n, unsigned long long* dev_counts,
+                         int64_t* dev_sums, unsigned long long* dev_missing_count) {
+    return index_accumulate(c, ix, dev_keys, key_stride, dev_values, value_stride, n, dev_counts, dev_sums, dev_missing_count);
 }
 
 int phj_index_info_get(const phj_index* ix, phj_index_info* out) {
@@ -4639,6 +4793,7 @@ void phj_index_destroy(phj_ctx* c, phj_index* ix) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);   // lookups still in the stream read the table
     if (ix->tab) (void)hipFree(ix->tab);
+    if (ix->first_rows) (void)hipFree(ix->first_rows);
     delete ix;
 }
 

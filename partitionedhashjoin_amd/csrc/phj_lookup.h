@@ -212,7 +212,14 @@ struct IxLookupArgs {
     int64_t* rows;               // out: the lowest build row of key i, or PHJ_NO_ROW
     uint8_t* found;              // out, optional: one byte per key
     unsigned long long* count;   // optional: found keys are added
+    const int64_t* first;        // IxMode::RowsVia: first_rows of the ordinal index (phj_ordinal.h)
 };
+
+// What a slot's 32-bit word is and what the lookup writes: Rows, a plain index:
+// the word is the row; Codes, an ordinal index (phj_ordinal.h): the word is the
+// key's ordinal and is written as it is (phj_index_encode); RowsVia, an ordinal
+// index asked for rows: one dependent read of first[ordinal] per hit.
+enum class IxMode { Rows = 0, Codes = 1, RowsVia = 2 };
 
 constexpr int kIxItems = kMemberItems;   // keys per lane and step (member_store's shape)
 
@@ -222,7 +229,7 @@ constexpr int kIxItems = kMemberItems;   // keys per lane and step (member_store
 // four 16-B loads: 64 registers of buckets per lane at four keys, so the kernel
 // is built for 4 waves per SIMD (the compiler's resource report: 97-99 VGPRs,
 // which allocate 104 and allow 4 waves either way; no scratch).
-template <int HK, int STRIDE>
+template <int HK, int STRIDE, IxMode MODE = IxMode::Rows>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ix_lookup(IxLookupArgs a) {
     constexpr int ITEMS = kIxItems;
     const ulonglong2* tab2 = reinterpret_cast<const ulonglong2*>(a.tab);
@@ -292,10 +299,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             }
         }
         hits += __popc(hitm);
+        if constexpr (MODE == IxMode::RowsVia) {   // every gather requested before any store
+            int64_t fr[ITEMS];
 #pragma unroll
-        for (int i = 0; i < ITEMS; i++)   // 8 B per lane: a wave instruction writes one 512-byte run
-            if ((vm >> i) & 1u)
-                a.rows[base + i * 256 + tid] = (hitm >> i) & 1u ? static_cast<int64_t>(row[i]) : int64_t{-1};
+            for (int i = 0; i < ITEMS; i++) fr[i] = (hitm >> i) & 1u ? a.first[row[i]] : int64_t{-1};
+#pragma unroll
+            for (int i = 0; i < ITEMS; i++)
+                if ((vm >> i) & 1u) a.rows[base + i * 256 + tid] = fr[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < ITEMS; i++)   // 8 B per lane: a wave instruction writes one 512-byte run
+                if ((vm >> i) & 1u)
+                    a.rows[base + i * 256 + tid] = (hitm >> i) & 1u ? static_cast<int64_t>(row[i]) : int64_t{-1};
+        }
         if (a.found) member_store(a.found, base, tid, hitm, vm);
     }
     if (a.count) member_count(hits, a.count);

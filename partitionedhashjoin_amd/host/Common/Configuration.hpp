@@ -78,6 +78,7 @@ struct GpuConfiguration {
     int Aggregate = 0;               // --aggregate totals | groups: 1 / 2, Run() reports the join's aggregates (phj_join_aggregate; 0 = off)
     uint32_t Member = 0;             // --member probe | build | both: Run() reports which rows have a partner (phj_join_member; PHJ_MEMBER_* set, 0 = off)
     uint32_t Lookup = 0;             // --lookup BATCHES: Run() builds a key index over tableA and looks tableB up in that many slices (phj_index_*; 0 = off)
+    uint32_t LookupAs = 0;           // --lookup-as rows | codes | groups (0 | 1 | 2): what --lookup computes per key (phj_index_lookup / _encode / _accumulate)
     bool Columns = false;            // --layout columns: both relations are split into key / payload columns on the device before the join (phj_relation_to_columns)
     std::vector<int> Devices;       // --gpus N / --devices a,b,..: the context's devices (empty: {Device})
     uint32_t ContextFlags = 0;       // --exchange rccl|local: PHJ_CTX_EXCHANGE / PHJ_CTX_LOCAL

@@ -213,8 +213,76 @@ inline void join_member(Device& dev, const phj_join_params& p, phj_join_result& 
 // scratch context (the C ABI has no allocator). r is the build's result with
 // matches = the keys found (== the count join's matches) and probe_ms = the
 // wall time of all lookups.
+// --lookup-as codes | groups (as = 1 | 2): the index is built with ordinals
+// (phj_index_build_ex). codes: phj_index_encode in place of the lookup, and
+// `lookup_codes_checksum` = Σ (i + 1) · (code[i] + 1) mod 2^64. groups:
+// phj_index_accumulate per slice with the probe payload as the value, into one
+// pair of accumulators: `groups` (= the distinct keys), `groups_count_checksum`
+// = Σ (j + 1) · count[j] and `groups_sum_checksum` = Σ (j + 1) · sum[j] mod
+// 2^64; keys_found = the keys less the device's missing count.
+inline void join_lookup_groups(Device& dev, const phj_join_params& p, phj_join_result& r, uint32_t batches,
+                               Common::IHashJoinTimer& timer) {
+    phj_ctx* c = dev.Get();
+    uint64_t nS = 0;
+    const int64_t *sk = nullptr, *sp = nullptr;
+    uint32_t stride = 1;
+    dev.Check(phj_relation_columns(c, PHJ_SIDE_PROBE, &sk, &sp, &nS));
+    if (!sk) {
+        sk = reinterpret_cast<const int64_t*>(phj_relation_device_ptr(c, PHJ_SIDE_PROBE, &nS));
+        sp = sk ? sk + 1 : nullptr;
+        stride = 2;
+    }
+    if (nS > 0 && !sp) throw std::runtime_error("--lookup-as groups sums the probe payloads: the probe side has none");
+    phj_index* ix = nullptr;
+    dev.Check(phj_index_build_ex(c, &p, PHJ_INDEX_ORDINALS, &ix, &r));
+    phj_index_info info{};
+    dev.Check(phj_index_info_get(ix, &info));
+    const uint64_t d = info.distinct;
+    Device scratch(dev.DeviceId());
+    const std::vector<int64_t> zeros(d + 1, 0);   // {counts | missing}, {sums}
+    scratch.Check(phj_relation_upload_columns(scratch.Get(), PHJ_SIDE_BUILD, zeros.data(), zeros.data(), zeros.size()));
+    const int64_t *cnt_c = nullptr, *sum_c = nullptr;
+    scratch.Check(phj_relation_columns(scratch.Get(), PHJ_SIDE_BUILD, &cnt_c, &sum_c, nullptr));
+    auto* counts = reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(cnt_c));
+    int64_t* sums = const_cast<int64_t*>(sum_c);
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t b = 0; b < batches; b++) {
+        const uint64_t lo = nS * b / batches, hi = nS * (b + 1) / batches;
+        dev.Check(phj_index_accumulate(c, ix, sk ? sk + stride * lo : nullptr, stride, sp ? sp + stride * lo : nullptr, stride,
+                                       hi - lo, counts, sums, counts + d));
+    }
+    dev.Check(phj_ctx_synchronize(c));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<phj_tuple> t(zeros.size());
+    scratch.Check(phj_relation_download(scratch.Get(), PHJ_SIDE_BUILD, t.data(), t.size()));
+    uint64_t csum = 0, ssum = 0, hits = 0;
+    for (uint64_t j = 0; j < d; j++) {
+        csum += (j + 1) * static_cast<uint64_t>(t[j].id);
+        ssum += (j + 1) * static_cast<uint64_t>(t[j].payload);
+        hits += static_cast<uint64_t>(t[j].id);
+    }
+    phj_index_destroy(c, ix);
+    if (hits + static_cast<uint64_t>(t[d].id) != nS)
+        throw std::runtime_error("--lookup-as groups: counts and the missing count do not add up to the keys");
+    timer.AddResult("lookup_as", "groups");
+    timer.AddResult("batches", std::to_string(batches));
+    timer.AddResult("keys_looked_up", std::to_string(nS));
+    timer.AddResult("keys_found", std::to_string(hits));
+    timer.AddResult("index_rows", std::to_string(info.rows));
+    timer.AddResult("index_distinct", std::to_string(info.distinct));
+    timer.AddResult("index_table_bytes", std::to_string(info.table_bytes));
+    timer.AddResult("index_build_us", std::to_string(static_cast<int64_t>(std::llround(r.build_ms * 1e3))));
+    timer.AddResult("lookup_batch_us", std::to_string(static_cast<int64_t>(std::llround(ms * 1e3 / batches))));
+    timer.AddResult("groups", std::to_string(d));
+    timer.AddResult("groups_count_checksum", std::to_string(csum));
+    timer.AddResult("groups_sum_checksum", std::to_string(ssum));
+    r.matches = hits;
+    r.probe_ms = ms;
+}
+
 inline void join_lookup(Device& dev, const phj_join_params& p, phj_join_result& r, uint32_t batches,
-                        Common::IHashJoinTimer& timer) {
+                        Common::IHashJoinTimer& timer, uint32_t as = 0) {
+    if (as == 2) return join_lookup_groups(dev, p, r, batches, timer);
     phj_ctx* c = dev.Get();
     uint64_t nS = 0;
     const int64_t *sk = nullptr, *sp = nullptr;
@@ -225,7 +293,8 @@ inline void join_lookup(Device& dev, const phj_join_params& p, phj_join_result& 
         stride = 2;
     }
     phj_index* ix = nullptr;
-    dev.Check(phj_index_build(c, &p, &ix, &r));
+    if (as == 1) dev.Check(phj_index_build_ex(c, &p, PHJ_INDEX_ORDINALS, &ix, &r));
+    else dev.Check(phj_index_build(c, &p, &ix, &r));
     phj_index_info info{};
     dev.Check(phj_index_info_get(ix, &info));
     Device scratch(dev.DeviceId());
@@ -240,7 +309,8 @@ inline void join_lookup(Device& dev, const phj_join_params& p, phj_join_result& 
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t b = 0; b < batches; b++) {
         const uint64_t lo = nS * b / batches, hi = nS * (b + 1) / batches;
-        dev.Check(phj_index_lookup(c, ix, sk ? sk + stride * lo : nullptr, stride, hi - lo, rows + lo, nullptr, cnt));
+        if (as == 1) dev.Check(phj_index_encode(c, ix, sk ? sk + stride * lo : nullptr, stride, hi - lo, rows + lo, nullptr, cnt));
+        else dev.Check(phj_index_lookup(c, ix, sk ? sk + stride * lo : nullptr, stride, hi - lo, rows + lo, nullptr, cnt));
     }
     dev.Check(phj_ctx_synchronize(c));
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -256,6 +326,7 @@ inline void join_lookup(Device& dev, const phj_join_params& p, phj_join_result& 
     phj_index_destroy(c, ix);
     if (static_cast<uint64_t>(found.id) != hits)
         throw std::runtime_error("--lookup: the device's found count differs from the rows it wrote");
+    if (as == 1) timer.AddResult("lookup_as", "codes");
     timer.AddResult("batches", std::to_string(batches));
     timer.AddResult("keys_looked_up", std::to_string(nS));
     timer.AddResult("keys_found", std::to_string(hits));
@@ -264,7 +335,7 @@ inline void join_lookup(Device& dev, const phj_join_params& p, phj_join_result& 
     timer.AddResult("index_table_bytes", std::to_string(info.table_bytes));
     timer.AddResult("index_build_us", std::to_string(static_cast<int64_t>(std::llround(r.build_ms * 1e3))));
     timer.AddResult("lookup_batch_us", std::to_string(static_cast<int64_t>(std::llround(ms * 1e3 / batches))));
-    timer.AddResult("lookup_rows_checksum", std::to_string(sum));
+    timer.AddResult(as == 1 ? "lookup_codes_checksum" : "lookup_rows_checksum", std::to_string(sum));
     r.matches = hits;
     r.probe_ms = ms;
 }
@@ -278,7 +349,7 @@ inline std::shared_ptr<Common::Table<Common::JoinedTuple>> join(Device& dev, con
                                                                 Common::IHashJoinTimer& timer) {
     const bool materialize = gpu.Materialize, all = gpu.MaterializeAll;
     if (gpu.Lookup != 0) {
-        join_lookup(dev, p, r, gpu.Lookup, timer);
+        join_lookup(dev, p, r, gpu.Lookup, timer, gpu.LookupAs);
         return std::make_shared<Common::Table<Common::JoinedTuple>>(Common::generate_uuid());
     }
     if (gpu.Member != 0) {

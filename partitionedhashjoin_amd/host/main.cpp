@@ -22,6 +22,7 @@
 //   --rows W              payloads|indices: how the returned rows are made (indices: an index join on the key columns, then gathers)
 //   --member M            probe|build|both: report which rows have a partner on the other side (counts and mask checksums)
 //   --lookup BATCHES      build a retained key index over tableA once, look tableB's keys up in BATCHES equal slices
+//   --lookup-as KIND      rows (default) | codes | groups: what --lookup computes per slice (lookup / encode / accumulate)
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -91,13 +92,20 @@ const char* kHelp =
     "                                      probe_matched, build_matched and, per asked side, a checksum of its mask,\n"
     "                                      sum of (i + 1) * mask[i] modulo 2^64. One device only, and not together\n"
     "                                      with returned rows or aggregates.\n"
-    "  --lookup arg                        BATCHES >= 1: build a retained key index over the primary relation once\n"
+    "  --lookup arg [--lookup-as arg]      BATCHES >= 1: build a retained key index over the primary relation once\n"
     "                                      (phj_index_build), then look the secondary relation's keys up in BATCHES\n"
     "                                      equal slices (phj_index_lookup, enqueued back to back): keys_looked_up,\n"
     "                                      keys_found (the count join's matches), index_distinct, index_build_us,\n"
     "                                      lookup_batch_us and a checksum of the rows, sum of (i + 1) * (row[i] + 1)\n"
     "                                      modulo 2^64. One device only, and not together with returned rows,\n"
     "                                      aggregates or membership masks.\n"
+    "                                      The second option (= rows) says what each slice computes: rows | codes |\n"
+    "                                      groups. codes: the index is built with ordinals (dense ids of the distinct\n"
+    "                                      keys in first-appearance order) and phj_index_encode writes them:\n"
+    "                                      lookup_codes_checksum, sum of (i + 1) * (code[i] + 1) modulo 2^64. groups:\n"
+    "                                      phj_index_accumulate counts the keys and sums their payloads per ordinal:\n"
+    "                                      groups, groups_count_checksum, sum of (j + 1) * count[j], and\n"
+    "                                      groups_sum_checksum, sum of (j + 1) * sum[j] modulo 2^64.\n"
     "  --gpus arg (=1)                     Devices --device .. --device+N-1: range-sharded relations,\n"
     "                                      RCCL exchange of the partitioned build side.\n"
     "  --devices arg                       Explicit device list a,b,... (instead of --gpus).\n"
@@ -132,7 +140,7 @@ Common::Configuration parseArguments(int argc, char** argv) {
     static const std::set<std::string> known = {"help", "primary", "secondary", "skew", "log", "join", "format",
                                                 "unit", "output", "filename", "partitions", "device", "gpus", "devices", "exchange", "hash",
                                                 "radix-bits", "seed", "hash-seed", "generate", "table-ratio",
-                                                "materialize", "join-kind", "aggregate", "layout", "rows", "member", "lookup"};
+                                                "materialize", "join-kind", "aggregate", "layout", "rows", "member", "lookup", "lookup-as"};
     Common::Configuration c{};
     c.OutputFormatConfig.TimeUnit = "ms";
     c.OutputConfig.File.Name = "hashjoin.txt";
@@ -223,6 +231,13 @@ Common::Configuration parseArguments(int argc, char** argv) {
             const long long b = parse_number<long long>("lookup", vm["lookup"]);
             if (b < 1 || b > 1000000) throw std::invalid_argument("--lookup takes 1..1000000 batches");
             c.GpuConfig.Lookup = static_cast<uint32_t>(b);
+        }
+        if (vm.count("lookup-as")) {
+            if (!vm.count("lookup")) throw std::invalid_argument("--lookup-as says what --lookup computes: give --lookup BATCHES");
+            if (vm["lookup-as"] == "codes") c.GpuConfig.LookupAs = 1;
+            else if (vm["lookup-as"] == "groups") c.GpuConfig.LookupAs = 2;
+            else if (vm["lookup-as"] != "rows")
+                throw std::invalid_argument("the argument ('" + vm["lookup-as"] + "') for option '--lookup-as' is invalid");
         }
         c.GpuConfig.Hash = PHJ_HASH_XXH3;
         if (vm.count("hash")) {

@@ -10,6 +10,7 @@
 #  `make build/libphj_nofuse.so HIPDEFS=-DPHJ_HOT_FUSE=0`: S's pass with the weight add and the rank claim as two LDS atomics;
 #  `make build/libphj_nobatch.so HIPDEFS=-DPHJ_P1_BATCH=0`: S's pre-aggregating pass with its sort stage once per input tile, not per 4096 kept codes;
 #  `HIPDEFS=-DPHJ_P1F_BUFLOAD=0` / `_SET128=0` / `_WTADDR=1` / `_FULL=0` / `_CMPBALLOT=0` / `_WAVEFAST=0`: the front of S's batched pass 1, one item each (csrc/phj_partition.h);
+#  `make build/libphj_acc0.so HIPDEFS=-DPHJ_IX_ACC_CACHE=0` (or =512 / =1024): k_ix_accumulate with plain global atomics / another cache size (scripts/ordinal_bench.py --acc-libs);
 #  `make build/libphj_col8.so HIPDEFS=-DPHJ_COL_LOAD16=0`: the column form of the code pass with 8-B loads (scripts/columns_bench.py))
 # The JSON lines go to $OUT (default ab_out/).
 set -o pipefail
