@@ -29,21 +29,10 @@
 #ifndef PHJ_PREAGG
 #define PHJ_PREAGG 1
 #endif
-// 1: with the hot-key pre-aggregation, R's chain runs on the aux stream beside
-// the hot-key prologue, on all but PHJ_HOT_FREE_CUS CUs per shard of its pass 1;
-// 0: after S's pass 1 on the main stream (the A/B leg, scripts/ab_lib.sh)
-#ifndef PHJ_HOT_EARLY_R
-#define PHJ_HOT_EARLY_R 1
-#endif
+// With the hot-key pre-aggregation, R's chain runs on the aux stream beside
+// the hot-key prologue, on all but PHJ_HOT_FREE_CUS CUs per shard of its pass 1
 #ifndef PHJ_HOT_FREE_CUS
 #define PHJ_HOT_FREE_CUS 6
-#endif
-// The column form of the 1024 x 4 code pass (a relation bound as columns): 0 =
-// 8 B per lane and load; 1 = 16 B, two neighbouring keys (the A/B leg,
-// scripts/ab_lib.sh: measured level with 8 B, DESIGN.md "Columnar relations";
-// a column of one key takes the 8-B form).
-#ifndef PHJ_COL_LOAD16
-#define PHJ_COL_LOAD16 0
 #endif
 #ifndef PHJ_P1_PROF
 #define PHJ_P1_PROF 0
@@ -269,7 +258,7 @@ struct phj_ctx {
     bool hot_on = false, hot_ran = false;
     uint64_t hot_n = 0;
     uint32_t hot_min_mass = 0;
-    // R's chain beside the hot-key prologue (PHJ_HOT_EARLY_R): the aux stream
+    // R's chain beside the hot-key prologue: the aux stream
     // waits for hot_fork (the main stream at the join's start), the main
     // stream for hot_join (the end of R's chain); p1_free_cus: CUs per shard
     // the chunked pass 1 launched next leaves free
@@ -724,29 +713,20 @@ int scan_u32(phj_ctx* c, uint32_t* data, uint32_t len, uint32_t narrays, uint32_
 // The pipelined code pass in 1024 x 4 workgroups: KPF tiles of keys in
 // flight (S: 2, measured 1.08 -> 1.05 ms at C2; R: 1); a measurement build
 // (-DPHJ_P1_PROF=1, scripts/ab_lib.sh) runs S's pass in the phase-clock form.
-// cols: the relation is a key column (k_chunk_codes_pipe COLS 1 / 2, one digit
+// cols: the relation is a key column (k_chunk_codes_pipe COLS 1, one digit
 // per thread only: cols_native).
 template <int HK, int DPT>
-const void* pipe1024(int kpf, bool hot = false, int cols = 0) {
-    // the HOT forms: batched by default (k_chunk_codes_pipe BATCH; -DPHJ_P1_BATCH=0: the per-tile form)
-    constexpr int kBatch = PHJ_PREAGG != 0 && PHJ_P1_BATCH != 0 ? 1 : 0;
-    (void)kBatch;
-    if constexpr (DPT == 1 && PHJ_COL_LOAD16 != 0) {
-        if (cols == 2) {
-            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, PHJ_PREAGG != 0 ? 1 : 0, 2, kBatch>);
-            if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 0, 2>);
-            return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 0, 2>);
-        }
+const void* pipe1024(int kpf, bool hot = false, bool cols = false) {
+    if constexpr (DPT == 1 && PHJ_PREAGG != 0) {   // the HOT form (phj_hot.h): S's pass counts the hot codes' weights
+        if (hot && kpf != 1)
+            return cols ? reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, 1, 1>)
+                        : reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, 1, 0>);
     }
     if constexpr (DPT == 1) {
-        if (cols != 0) {
-            if (PHJ_PREAGG != 0 && hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, PHJ_PREAGG != 0 ? 1 : 0, 1, kBatch>);
+        if (cols) {
             if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 1, 0, 1>);
             return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, false, 2, 0, 1>);
         }
-    }
-    if constexpr (DPT == 1 && PHJ_PREAGG != 0) {   // the HOT form (phj_hot.h): S's pass counts the hot codes' weights
-        if (hot && kpf != 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, 1, 0, PHJ_P1_PROF != 0, 2, 1, 0, kBatch>);
     }
     if (kpf == 1) return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, false, 1>);
     return reinterpret_cast<const void*>(&k_chunk_codes_pipe<1024, 4, HK, DPT, 0, PHJ_P1_PROF != 0, 2>);
@@ -834,8 +814,8 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
                         const int kpf = is_r ? 1 : 2;
                         if (hot && dpt == 4) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation: more digits than threads");
                         if (c->p1_cols && dpt == 4) return set_err(c, PHJ_ERR_STATE, "key column: more digits than threads");
-                        const int cols = !c->p1_cols ? 0 : PHJ_COL_LOAD16 != 0 && n >= 2 ? 2 : 1;
-                        cols_form = cols != 0;
+                        const bool cols = c->p1_cols;
+                        cols_form = cols;
                         kfn = with_hash(hk, [&](auto h) {
                             constexpr int HK = decltype(h)::value;
                             return dpt == 4 ? pipe1024<HK, 2>(kpf) : pipe1024<HK, 1>(kpf, hot, cols);
@@ -4256,14 +4236,14 @@ int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         // after S's pass (PHJ_R_ORDER=1, default) R's chain runs on the main
         // stream itself: nothing runs beside it, and a cross-stream event wait
         // before the probe costs ~15 us (measured gap, r05z timeline)
-        // with the hot-key pre-aggregation (phj_hot.h, PHJ_HOT_EARLY_R): R's
+        // with the hot-key pre-aggregation (phj_hot.h): R's
         // chain on the aux stream from the join's start, beside the hot-key
         // prologue (a few narrow kernels bound by atomics), its pass 1 leaving
         // the prologue PHJ_HOT_FREE_CUS CUs per shard; the main stream waits
         // for it before the LDS join. R's chain reads nothing of S's: the
         // weights are resolved by the LDS join, not by R's pass
         const bool hot = hot_wanted(c, cpl, S.n, R.n);
-        const bool early_r = PHJ_HOT_EARLY_R != 0 && hot && R.n > 0;
+        const bool early_r = hot && R.n > 0;
         auto r_chain = [&](hipEvent_t after) -> int {
             if (!r_main || early_r) {
                 PHJ_HIP(c, hipStreamWaitEvent(c->aux, after, 0));

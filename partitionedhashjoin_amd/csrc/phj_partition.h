@@ -153,31 +153,6 @@ constexpr int kP1ProfWords = 16;
 // the hot table: every digit has kHotSub sets (chosen by the code's top bit)
 // of kHotWays ways, so a lookup is one 16-B LDS read
 constexpr uint32_t kHotWays = 2, kHotSub = 2, kHotPer = kHotWays * kHotSub;
-#ifndef PHJ_HOT_FUSE   // S's pass, HOT 1: a code's weight add and rank claim are one LDS atomic (0: two, the A/B leg)
-#define PHJ_HOT_FUSE 1
-#endif
-#ifndef PHJ_P1_BATCH   // S's pass, HOT 1: the sort stage once per T kept codes (0: once per input tile, the A/B leg)
-#define PHJ_P1_BATCH 1
-#endif
-// The batched loop's front (hash to barrier A), one A/B leg each (0: as before):
-#ifndef PHJ_P1F_BUFLOAD  // the pipelined code pass's key loads (every form but COLS 2) as buffer loads off a per-tile scalar descriptor
-#define PHJ_P1F_BUFLOAD 1
-#endif
-#ifndef PHJ_P1F_SET128  // every set read is one 16-B LDS read (the compiler split item 0's and read its last word behind a branch)
-#define PHJ_P1F_SET128 1
-#endif
-#ifndef PHJ_P1F_WTADDR   // 1: a set's weights lie 16 B behind its codes, the weight add's address is the lookup's plus a constant (measured level, 16 KB more LDS at 1024 digits: off)
-#define PHJ_P1F_WTADDR 0
-#endif
-#ifndef PHJ_P1F_FULL     // a whole tile compiles no validity compare into the lookups and the append
-#define PHJ_P1F_FULL 1
-#endif
-#ifndef PHJ_P1F_CMPBALLOT // the kept codes' ballot put together from the ballots of the four plain compares of a lookup
-#define PHJ_P1F_CMPBALLOT 1
-#endif
-#ifndef PHJ_P1F_WAVEFAST // append: a wave whose indices all lie in the batch being filled does no range compare and holds nothing
-#define PHJ_P1F_WAVEFAST 1
-#endif
 constexpr uint32_t kHotCtlEntries = 0, kHotCtlMass = 1;   // hot_ctl words: entries, sampled keys they cover
 
 // Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md,
@@ -1176,14 +1151,12 @@ __host__ __device__ constexpr size_t chunk_pipe_lds_bytes(int T, uint32_t nb) {
 // ... and after them the HOT form's copy of the hot table: the codes, the
 // workgroup's 32-bit weights and a word per thread (1024 of them: hown[],
 // the target of the per-tile loop's adds of 0. The batched loop does not use
-// it, but a BATCH kernel still runs the per-tile loop with its HOT 1 adds when
-// the table is off at run time, so the 4 KB stay in every HOT form)
-// PHJ_P1F_WTADDR: the table is laid by sets of kHotSetBytes: a set's kHotWays
-// codes (the 16-B read), their kHotWays weights, 8 B unused. The weight of a
-// matched way is then at the lookup's address + 16 + 4 * way: nothing to
-// rebuild from the table's base inside the exec-masked add. (0: all codes,
-// then all weights.)
-constexpr uint32_t kHotSetBytes = PHJ_P1F_WTADDR ? 32 : 12 * kHotWays;
+// it, but the HOT kernel still runs the per-tile loop with its HOT 1 adds when
+// the table is off at run time, so the 4 KB stay).
+// The table is all codes (a set's kHotWays codes are the 16-B read), then all
+// weights: kHotSetBytes of LDS per set. (Weights 16 B behind their set's codes
+// measured level and cost 16 KB more LDS at 1024 digits.)
+constexpr uint32_t kHotSetBytes = 12 * kHotWays;
 __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int hot) {
     return hot == 0 ? 0 : static_cast<size_t>(nb) * kHotSub * kHotSetBytes + 4096;
 }
@@ -1207,10 +1180,11 @@ __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int h
 // same test as the LDS join's: they read the same words).
 // COLS (a relation bound as columns, phj_relation_bind_columns): a.in_keys is
 // the key column, not the tuples. 1: 8 B per lane and load (a wave's load
-// covers 512 contiguous bytes); 2: 16 B, two neighbouring keys per lane, half
-// the load instructions, items 2p and 2p + 1 of a lane then being neighbours
-// (pipe_elem). 0: tuples, the code as before the column forms.
-// BATCH (HOT 1 with the table on at run time; off: the per-tile loop below):
+// covers 512 contiguous bytes; 16-B loads of two neighbouring keys measured
+// level). 0: tuples. Either way item i of a lane is element
+// wbase + i * 64 + lane of the tile.
+// The batched loop (HOT 1 with the table on at run time; off: the per-tile
+// loop below; one digit per thread, T a power of two):
 // the sort stage (rank, scan, claims, LDS scatter, protocol, write-out) runs
 // once per T KEPT codes, not once per input tile. A loop iteration is still
 // one input tile: hash, lookups, weight adds (no return value), and every kept
@@ -1232,49 +1206,42 @@ __host__ __device__ constexpr size_t chunk_pipe_hot_lds_bytes(uint32_t nb, int h
 // partial batch (the write-out's past() form) and is resolved in one more
 // iteration. Words tmp[21 + parity]: kept codes appended in the iterations of
 // that parity, never reset (read after A, added to again two iterations on).
-// The front of an iteration (PHJ_P1F_*, each an A/B leg): after the hash and
-// the next tile's loads, a whole tile (cnt == T) takes a form of the lookups
-// and the append with no validity compare; the kept predicates stay lane
-// masks, and their ballots are put together in scalar registers from the
-// ballots of the lookup's four plain compares; a wave whose indices all lie
-// in the batch being filled (a wave-uniform test, no barrier inside) stores
-// at (scalar base) + 8 * mbcnt with no range compare and holds nothing, the
-// wave that crosses the batch's end takes the general path.
-// Key loads (PHJ_P1F_BUFLOAD, every form but COLS 2): buffer loads off a
-// descriptor built per tile in scalar registers (base = the tile's first
-// element: 64-bit, so relations beyond 4 GiB; size = the tile's valid bytes),
-// one per-lane offset and the items' distances as immediates. A lane past the
-// relation's end reads 0, never a tuple: validity comes from cnt alone.
-typedef long long key_pair __attribute__((ext_vector_type(2), aligned(8)));   // 16 B loaded from an 8-B aligned column
+// The front of an iteration (hash to barrier A; each item measured, DESIGN.md
+// round 11): after the hash and the next tile's loads, every set read is one
+// 16-B LDS read; a whole tile (cnt == T) takes a form of the lookups and the
+// append with no validity compare; the kept predicates stay lane masks, and
+// their ballots are put together in scalar registers from the ballots of the
+// lookup's four plain compares; a wave whose indices all lie in the batch
+// being filled (a wave-uniform test, no barrier inside) stores at (scalar
+// base) + 8 * mbcnt with no range compare and holds nothing, the wave that
+// crosses the batch's end takes the general path.
+// Key loads (every form): buffer loads off a descriptor built per tile in
+// scalar registers (base = the tile's first element: 64-bit, so relations
+// beyond 4 GiB; size = the tile's valid bytes), one per-lane offset and the
+// items' distances as immediates. A lane past the relation's end reads 0,
+// never a tuple: validity comes from cnt alone.
 typedef uint32_t hot_set_t __attribute__((ext_vector_type(4)));   // a set of the hot table: kHotWays 64-bit codes
-// element of the tile that is item i of a lane
-template <int COLS>
-__device__ __forceinline__ uint32_t pipe_elem(uint32_t wbase, uint32_t lane, int i) {
-    if constexpr (COLS == 2) return wbase + static_cast<uint32_t>(i >> 1) * 128 + lane * 2 + static_cast<uint32_t>(i & 1);
-    else return wbase + i * 64 + lane;
-}
-template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0, int COLS = 0, int BATCH = 0>
+template <int BLOCK, int ITEMS, int HK, int DPT = 1, int WPE = 0, bool PROF = false, int KPF = 1, int HOT = 0, int COLS = 0>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : BLOCK / 256)))
 void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     constexpr int NW = BLOCK / 64;
     constexpr int T = BLOCK * ITEMS;
     static_assert(NW <= 16, "scan words [0, NW) below the reservation words");
     static_assert(HOT == 0 || HOT == 1, "HOT 1: S's pre-aggregating pass");
-    static_assert(BATCH == 0 || (HOT == 1 && DPT == 1 && (T & (T - 1)) == 0), "BATCH: the HOT 1 form, one digit per thread, ring slot = index mod 2T");
+    static_assert(HOT == 0 || (DPT == 1 && (T & (T - 1)) == 0), "HOT 1 (the batched loop): one digit per thread, ring slot = index mod 2T");
+    static_assert(COLS == 0 || COLS == 1, "tuples or the key column");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t nb = a.nbins;   // host: nb <= DPT * BLOCK
     int64_t* sbuf = reinterpret_cast<int64_t*>(smem);                       // [2][T] sorted codes
     uint32_t* wcnt = reinterpret_cast<uint32_t*>(sbuf + 2 * T);             // [2][nb] counter rows
     uint4* wdesc = reinterpret_cast<uint4*>(wcnt + (2 * nb + 3u) / 4 * 4);  // [nb] {k < split: slot - k, else, split}
-    uint32_t* tmp = reinterpret_cast<uint32_t*>(wdesc + nb);                // [0, NW) scan; 16-19 reservations [2]; 20 bad tile; 21-22 BATCH: kept codes appended [parity]
+    uint32_t* tmp = reinterpret_cast<uint32_t*>(wdesc + nb);                // [0, NW) scan; 16-19 reservations [2]; 20 bad tile; 21-22 the batched loop: kept codes appended [parity]
     // HOT: the hot table's codes and (HOT 1) their weights in this workgroup
     // (chunk_pipe_hot_lds_bytes). Set s = digit * kHotSub + the code's top
     // bit; entry = s * kHotWays + way; byte offsets from hbase
     unsigned char* const hbase = reinterpret_cast<unsigned char*>(tmp + 32);
-    auto hot_set_off = [&](uint32_t s) -> uint32_t { return PHJ_P1F_WTADDR ? s * kHotSetBytes : s * (kHotWays * 8); };
-    auto hot_wt_off = [&](uint32_t s, uint32_t way) -> uint32_t {
-        return PHJ_P1F_WTADDR ? s * kHotSetBytes + kHotWays * 8 + way * 4 : nb * kHotPer * 8 + (s * kHotWays + way) * 4;
-    };
+    auto hot_set_off = [&](uint32_t s) -> uint32_t { return s * (kHotWays * 8); };
+    auto hot_wt_off = [&](uint32_t s, uint32_t way) -> uint32_t { return nb * kHotPer * 8 + (s * kHotWays + way) * 4; };
     auto hot_code = [&](uint32_t entry) { return reinterpret_cast<unsigned long long*>(hbase + hot_set_off(entry / kHotWays)) + entry % kHotWays; };
     auto hot_wt = [&](uint32_t off) { return reinterpret_cast<uint32_t*>(hbase + off); };
     uint32_t* hown = reinterpret_cast<uint32_t*>(hbase + static_cast<size_t>(nb) * kHotSub * kHotSetBytes);   // HOT 1: [BLOCK] a word per lane for the adds of 0
@@ -1344,77 +1311,40 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     // KPF register buffers of keys used in turn (the loop unrolled KPF times,
     // so no register moves): tile t's keys were requested KPF tiles earlier
     int64_t key[KPF][ITEMS];
-    const longlong2* rel = reinterpret_cast<const longlong2*>(a.in_keys);
-    // item i of a lane is element pipe_elem(i) of the tile. Tuples and the
-    // 8-B column form: a wave's load covers 64 consecutive elements. COLS 2:
-    // a lane's 16-B load brings two neighbouring keys, items 2p and 2p + 1.
-    static_assert(COLS == 0 || COLS == 1 || (COLS == 2 && ITEMS % 2 == 0), "COLS 2: whole pairs per lane");
-#if PHJ_P1F_BUFLOAD
-    // the lane's byte offset in a tile (made opaque at each use: the items'
+    // item i of a lane is element wbase + i * 64 + lane of the tile: a wave's
+    // load covers 64 consecutive elements (tuples, or keys of the column).
+    // The lane's byte offset in a tile (made opaque at each use: the items'
     // distances then stay constants added beside the load, which takes them
     // as immediates, rather than four offsets hoisted into registers)
     const uint32_t bvo0 = (wbase + lane) * (COLS == 1 ? 8u : 16u);
-#endif
     auto load = [&](int64_t* k, uint32_t t) {
-#if PHJ_P1F_BUFLOAD
-        if constexpr (COLS != 2) {
-            // buffer loads: the tile's descriptor in scalar registers (base =
-            // the tile's first element, so a relation beyond 4 GiB is reached;
-            // size = the tile's valid bytes), one per-lane offset for the whole
-            // kernel and the item's distance in the instruction's immediate.
-            // No address arithmetic per key and no clamp: a lane past the
-            // relation's end reads 0, and validity comes from cnt alone
-            constexpr uint32_t ESZ = COLS == 1 ? 8 : 16;
-            const uint32_t tu = __builtin_amdgcn_readfirstlane(t);
-            const uint32_t lo = tu * T;
-            const unsigned char* base = reinterpret_cast<const unsigned char*>(a.in_keys) + static_cast<size_t>(lo) * ESZ;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<unsigned char*>(base), 0, static_cast<int>(min(static_cast<uint32_t>(T), a.n - lo) * ESZ), 0x00020000);
-            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-            u32x2 v[ITEMS];
-            uint32_t bvo = bvo0;
-            if (a.nt_load) {
-                __asm__ volatile("" : "+v"(bvo));
+        // buffer loads: the tile's descriptor in scalar registers (base =
+        // the tile's first element, so a relation beyond 4 GiB is reached;
+        // size = the tile's valid bytes), one per-lane offset for the whole
+        // kernel and the item's distance in the instruction's immediate.
+        // No address arithmetic per key and no clamp: a lane past the
+        // relation's end reads 0, and validity comes from cnt alone
+        constexpr uint32_t ESZ = COLS == 1 ? 8 : 16;
+        const uint32_t tu = __builtin_amdgcn_readfirstlane(t);
+        const uint32_t lo = tu * T;
+        const unsigned char* base = reinterpret_cast<const unsigned char*>(a.in_keys) + static_cast<size_t>(lo) * ESZ;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<unsigned char*>(base), 0, static_cast<int>(min(static_cast<uint32_t>(T), a.n - lo) * ESZ), 0x00020000);
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        u32x2 v[ITEMS];
+        uint32_t bvo = bvo0;
+        if (a.nt_load) {
+            __asm__ volatile("" : "+v"(bvo));
 #pragma unroll
-                for (int i = 0; i < ITEMS; i++) v[i] = __builtin_amdgcn_raw_buffer_load_b64(rs, bvo + static_cast<uint32_t>(i) * 64 * ESZ, 0, 2);
-            } else {
-                __asm__ volatile("" : "+v"(bvo));
-#pragma unroll
-                for (int i = 0; i < ITEMS; i++) v[i] = __builtin_amdgcn_raw_buffer_load_b64(rs, bvo + static_cast<uint32_t>(i) * 64 * ESZ, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < ITEMS; i++) k[i] = static_cast<int64_t>(static_cast<uint64_t>(v[i].x) | (static_cast<uint64_t>(v[i].y) << 32));
-            return;
-        }
-#endif
-        const uint32_t lo = t * T;
-        if constexpr (COLS == 2) {
-            // the pair clamped to the column's last two keys (host: n >= 2):
-            // only the last key of an odd column then arrives in the pair's
-            // second half (hash_all's tail); 8-B aligned, so any key column serves
-#pragma unroll
-            for (int p = 0; p < ITEMS / 2; p++) {
-                const uint32_t ix = min(lo + pipe_elem<COLS>(wbase, lane, 2 * p), a.n - 2);
-                const key_pair* src = reinterpret_cast<const key_pair*>(a.in_keys + ix);
-                const key_pair v = a.nt_load ? __builtin_nontemporal_load(src) : *src;
-                k[2 * p] = v.x;
-                k[2 * p + 1] = v.y;
-            }
+            for (int i = 0; i < ITEMS; i++) v[i] = __builtin_amdgcn_raw_buffer_load_b64(rs, bvo + static_cast<uint32_t>(i) * 64 * ESZ, 0, 2);
         } else {
+            __asm__ volatile("" : "+v"(bvo));
 #pragma unroll
-            for (int i = 0; i < ITEMS; i++) {
-                const uint32_t ix = min(lo + pipe_elem<COLS>(wbase, lane, i), a.n - 1);
-                if constexpr (COLS == 1) {
-                    if (a.nt_load) k[i] = __builtin_nontemporal_load(&a.in_keys[ix]);
-                    else k[i] = a.in_keys[ix];
-                } else {
-                    if (a.nt_load) k[i] = __builtin_nontemporal_load(&rel[ix].x);
-                    else k[i] = rel[ix].x;
-                }
-            }
+            for (int i = 0; i < ITEMS; i++) v[i] = __builtin_amdgcn_raw_buffer_load_b64(rs, bvo + static_cast<uint32_t>(i) * 64 * ESZ, 0, 0);
         }
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) k[i] = static_cast<int64_t>(static_cast<uint64_t>(v[i].x) | (static_cast<uint64_t>(v[i].y) << 32));
     };
-    (void)rel;
 
     for (uint32_t i = tid; i < 2 * nb; i += BLOCK) wcnt[i] = 0;
 #pragma unroll
@@ -1430,8 +1360,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                 *hot_code(i) = a.hot_code[i];
                 if constexpr (HOT == 1) *hot_wt(hot_wt_off(i / kHotWays, i % kHotWays)) = 0;
             }
-        if constexpr (BATCH != 0)
-            if (tid == 0) tmp[21] = tmp[22] = 0;   // (tmp[20] is reset by every close before it is read)
+        if (tid == 0) tmp[21] = tmp[22] = 0;   // (tmp[20] is reset by every close before it is read)
     }
     {
 #pragma unroll
@@ -1460,7 +1389,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
     uint32_t pcnt = 0, par = 0;
     const uint32_t d0 = tid * DPT;
     if (PROF) pc0 = px = clock64();
-    if constexpr (BATCH != 0) {
+    if constexpr (HOT == 1) {
         if (hot) {   // (the header comment's batched loop; workgroup-uniform)
             const uint32_t tile0 = tile;
             uint32_t gtot = 0;            // kept codes appended before this iteration ...
@@ -1493,15 +1422,9 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                     auto hash_all = [&](auto form, auto full) {
 #pragma unroll
                         for (int i = 0; i < ITEMS; i++) {
-                            uint64_t h;
-                            if constexpr (COLS == 2 && !decltype(full)::value) {
-                                const bool tail = (i & 1) == 0 && pipe_elem<COLS>(wbase, lane, i) + 1 == cnt;
-                                h = hash64<HK>(static_cast<uint64_t>(tail ? key[kb][i | 1] : key[kb][i]), a.f.seed);
-                            } else {
-                                h = hash64<HK>(static_cast<uint64_t>(key[kb][i]), a.f.seed);
-                            }
+                            const uint64_t h = hash64<HK>(static_cast<uint64_t>(key[kb][i]), a.f.seed);
                             code[i] = static_cast<int64_t>(h);
-                            dig[i] = decltype(full)::value || pipe_elem<COLS>(wbase, lane, i) < cnt ? code_digit(h, form) : 0u;
+                            dig[i] = decltype(full)::value || wbase + i * 64 + lane < cnt ? code_digit(h, form) : 0u;
                         }
                     };
                     if (dform == 2 && cnt == static_cast<uint32_t>(T)) hash_all(F2{}, std::true_type{});
@@ -1529,13 +1452,11 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                         // (the whole set is used here, to the compiler's eyes: the read
                         // stays one 16-B read, none of its words sunk behind a branch.
                         // An empty statement: no instruction and no wait of its own)
-                        if constexpr (PHJ_P1F_SET128 != 0) {
 #pragma unroll
-                            for (int i = 0; i < ITEMS; i++) __asm__ volatile("" ::"v"(set[i]));
-                        }
+                        for (int i = 0; i < ITEMS; i++) __asm__ volatile("" ::"v"(set[i]));
 #pragma unroll
                         for (int i = 0; i < ITEMS; i++) {
-                            const bool valid = decltype(full)::value || pipe_elem<COLS>(wbase, lane, i) < cnt;
+                            const bool valid = decltype(full)::value || wbase + i * 64 + lane < cnt;
                             const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
                             const bool x0 = set[i].x == lo, y0 = set[i].y == hi, x1 = set[i].z == lo, y1 = set[i].w == hi;
                             const bool m0 = x0 && y0, m1 = x1 && y1;
@@ -1543,15 +1464,11 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                             // (the kept codes' ballot from the ballots of the four plain
                             // compares, each the compare's own lane mask: the ballot of a
                             // combined predicate is rebuilt through a VGPR, two VALU more)
-                            if constexpr (PHJ_P1F_CMPBALLOT != 0) {
-                                const uint64_t bm = (__builtin_amdgcn_ballot_w64(x0) & __builtin_amdgcn_ballot_w64(y0)) |
-                                                    (__builtin_amdgcn_ballot_w64(x1) & __builtin_amdgcn_ballot_w64(y1));
-                                kb[i] = ~bm & __builtin_amdgcn_ballot_w64(valid);
-                            }
-                            if (m) {
-                                if constexpr (PHJ_P1F_WTADDR != 0) atomicAdd(hot_wt(so[i] + (m0 ? kHotWays * 8 : kHotWays * 8 + 4)), 1u);
-                                else atomicAdd(hot_wt(nb * kHotPer * 8 + (so[i] >> 1) + (m0 ? 0u : 4u)), 1u);
-                            }
+                            const uint64_t bm = (__builtin_amdgcn_ballot_w64(x0) & __builtin_amdgcn_ballot_w64(y0)) |
+                                                (__builtin_amdgcn_ballot_w64(x1) & __builtin_amdgcn_ballot_w64(y1));
+                            kb[i] = ~bm & __builtin_amdgcn_ballot_w64(valid);
+                            // (hot_wt_off of the matched way, from the set's offset)
+                            if (m) atomicAdd(hot_wt(nb * kHotPer * 8 + (so[i] >> 1) + (m0 ? 0u : 4u)), 1u);
                             keep[i] = valid && !m;
                         }
                         ptick(0);
@@ -1560,10 +1477,9 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                         uint32_t mb[ITEMS], pre[ITEMS], wtot = 0;
 #pragma unroll
                         for (int i = 0; i < ITEMS; i++) {
-                            const uint64_t b = PHJ_P1F_CMPBALLOT != 0 ? kb[i] : __builtin_amdgcn_ballot_w64(keep[i]);
-                            mb[i] = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u));
+                            mb[i] = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(kb[i] >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(kb[i]), 0u));
                             pre[i] = wtot;
-                            wtot += static_cast<uint32_t>(__popcll(b));
+                            wtot += static_cast<uint32_t>(__popcll(kb[i]));
                         }
                         uint32_t wbase_g = 0;
                         if (lane == 0) wbase_g = atomicAdd(&tmp[21 + cb], wtot);
@@ -1573,7 +1489,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                         // gsort is a multiple of T: inside the batch the wave's slots do
                         // not wrap around the ring, and a slot's address is one shift-add
                         // onto a scalar)
-                        if (PHJ_P1F_WAVEFAST != 0 && wbase_g + wtot - gsort <= static_cast<uint32_t>(T)) {
+                        if (wbase_g + wtot - gsort <= static_cast<uint32_t>(T)) {
                             int64_t* const wslot = sbuf + (wbase_g & (2 * T - 1));
 #pragma unroll
                             for (int i = 0; i < ITEMS; i++)
@@ -1589,7 +1505,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
                         }
                         ptick(1);
                     };
-                    if (PHJ_P1F_FULL != 0 && cnt == static_cast<uint32_t>(T)) rest(std::true_type{});
+                    if (cnt == static_cast<uint32_t>(T)) rest(std::true_type{});
                     else rest(std::false_type{});
                 }
                 const uint32_t pp = (nbat - 1) & 1u;   // the pending batch's half, row and words
@@ -1806,16 +1722,9 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             auto hash_all = [&](auto form, auto full) {
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
-                    uint64_t h;
-                    if constexpr (COLS == 2 && !decltype(full)::value) {
-                        // (load's clamp: an odd column's last key is the second of its pair)
-                        const bool tail = (i & 1) == 0 && pipe_elem<COLS>(wbase, lane, i) + 1 == cnt;
-                        h = hash64<HK>(static_cast<uint64_t>(tail ? key[kb][i | 1] : key[kb][i]), a.f.seed);
-                    } else {
-                        h = hash64<HK>(static_cast<uint64_t>(key[kb][i]), a.f.seed);
-                    }
+                    const uint64_t h = hash64<HK>(static_cast<uint64_t>(key[kb][i]), a.f.seed);
                     code[i] = static_cast<int64_t>(h);
-                    dig[i] = decltype(full)::value || pipe_elem<COLS>(wbase, lane, i) < cnt ? code_digit(h, form) : 0u;
+                    dig[i] = decltype(full)::value || wbase + i * 64 + lane < cnt ? code_digit(h, form) : 0u;
                 }
             };
             if (dform == 2 && cnt == static_cast<uint32_t>(T)) hash_all(F2{}, std::true_type{});
@@ -1824,69 +1733,24 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             else hash_all(F0{}, std::false_type{});
             const uint32_t ahead = tile + KPF * slots;
             load(key[kb], ahead < t_end ? ahead : tile);
-            uint32_t hm = 0;        // HOT 1: bit i = item i is a hot code ...
-            uint32_t hew[ITEMS];    // ... of this entry
-            (void)hm, (void)hew;
-            if constexpr (HOT != 0) {
-#pragma unroll
-                for (int i = 0; i < ITEMS; i++) {
-                    keep |= (pipe_elem<COLS>(wbase, lane, i) < cnt ? 1u : 0u) << i;
-                    hew[i] = 0;
-                }
-                if (hot) {
-                    // every set read first, then the compares: no branch per
-                    // code (a branch waits for its own LDS read: four round
-                    // trips a tile, measured +0.04 ms on S's pass)
-                    static_assert(kHotWays == 2, "a set is one 16-B read");
-                    static_assert(HOT != 1 || BLOCK <= 1024, "chunk_pipe_hot_lds_bytes: a word per thread");
-                    uint4 set[ITEMS];
-                    uint32_t e[ITEMS];
-#pragma unroll
-                    for (int i = 0; i < ITEMS; i++) {
-                        e[i] = dig[i] * kHotSub + static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 63);
-                        set[i] = *reinterpret_cast<const uint4*>(hbase + hot_set_off(e[i]));
-                    }
-#pragma unroll
-                    for (int i = 0; i < ITEMS; i++) {
-                        const uint32_t lo = static_cast<uint32_t>(code[i]), hi = static_cast<uint32_t>(static_cast<uint64_t>(code[i]) >> 32);
-                        const bool m0 = set[i].x == lo && set[i].y == hi, m1 = set[i].z == lo && set[i].w == hi;
-                        const bool m = (m0 || m1) && ((keep >> i) & 1u) != 0;
-                        hew[i] = hot_wt_off(e[i], m0 ? 0u : 1u);
-                        hm |= (m ? 1u : 0u) << i;
-                    }
-                    if constexpr (HOT == 1) keep &= ~hm;
-                }
-            }
             if constexpr (HOT == 1) {
-#if PHJ_HOT_FUSE
-                // one LDS atomic per code: a hot code counts into its entry's
-                // weight, a kept one claims its rank, any other adds 0 to the
-                // lane's own word (not to its digit's counter, where a hot key's
-                // lanes would still queue). Only a kept code's rank is read
+                // (the table is off at run time here: the batched loop above
+                // took every workgroup whose table is on, so nothing is looked up)
+                static_assert(kHotWays == 2, "a set is one 16-B read");
+                static_assert(BLOCK <= 1024, "chunk_pipe_hot_lds_bytes: a word per thread");
 #pragma unroll
-                for (int i = 0; i < ITEMS; i++) {
-                    const bool m = ((hm >> i) & 1u) != 0, k = ((keep >> i) & 1u) != 0;
-                    rank[i] = atomicAdd(m ? hot_wt(hew[i]) : k ? &crow[dig[i]] : &hown[tid], m || k ? 1u : 0u);
-                }
-#else
-                // the weight add (a lane without a match adds 0 to a word of its
-                // own), then the rank claim (a dropped code claims none)
-                if (hot) {
-#pragma unroll
-                    for (int i = 0; i < ITEMS; i++) {
-                        const bool m = ((hm >> i) & 1u) != 0;
-                        atomicAdd(m ? hot_wt(hew[i]) : &hown[tid], m ? 1u : 0u);
-                    }
-                }
+                for (int i = 0; i < ITEMS; i++) keep |= (wbase + i * 64 + lane < cnt ? 1u : 0u) << i;
+                // one LDS atomic per code: a kept one claims its rank, any other
+                // adds 0 to the lane's own word (not to its digit's counter).
+                // Only a kept code's rank is read
 #pragma unroll
                 for (int i = 0; i < ITEMS; i++) {
                     const bool k = ((keep >> i) & 1u) != 0;
                     rank[i] = atomicAdd(k ? &crow[dig[i]] : &hown[tid], k ? 1u : 0u);
                 }
-#endif
             } else {
 #pragma unroll
-                for (int i = 0; i < ITEMS; i++) rank[i] = atomicAdd(&crow[dig[i]], pipe_elem<COLS>(wbase, lane, i) < cnt ? 1u : 0u);
+                for (int i = 0; i < ITEMS; i++) rank[i] = atomicAdd(&crow[dig[i]], wbase + i * 64 + lane < cnt ? 1u : 0u);
             }
         }
         ptick(0);
@@ -1943,7 +1807,7 @@ void k_chunk_codes_pipe(PassArgs a, uint32_t ntiles, uint32_t per) {
             for (int i = 0; i < ITEMS; i++) base[i] = crow[dig[i]];
 #pragma unroll
             for (int i = 0; i < ITEMS; i++)
-                if (HOT == 1 ? ((keep >> i) & 1u) != 0 : pipe_elem<COLS>(wbase, lane, i) < cnt) sbuf[par * T + base[i] + rank[i]] = code[i];
+                if (HOT == 1 ? ((keep >> i) & 1u) != 0 : wbase + i * 64 + lane < cnt) sbuf[par * T + base[i] + rank[i]] = code[i];
         }
         const uint32_t pp = par ^ 1u;   // the previous tile's buffers
         // the next tile's counter row: the previous tile's, no longer read

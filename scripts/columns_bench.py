@@ -15,9 +15,6 @@ with their bytes from the deferred report, R.p1.scatter from one extra join
 with every timer on, S's pass in GB/s of its accounted bytes and as a share of
 the HBM peak, and relation_info.packed (0: no tuple copy was made).
 
-The load width of the column form is compiled in (PHJ_COL_LOAD16): run the
-script once per build, PHJ_LIB=build/libphj_NAME.so, to compare the two.
-
 One JSON document: --out FILE (default: stdout only)."""
 import argparse
 import json

@@ -177,10 +177,7 @@ def test_cold_codes_in_one_cluster(forced):
 
 def test_key_columns(forced):
     """The key-column form of the pass on one Zipf case (bound as
-    tests/test_gpu_columns.py binds them). This runs COLS 1 only, the 8-B
-    loads of the shipped build (PHJ_COL_LOAD16 is 0 there). The batched COLS 2
-    form exists only in a -DPHJ_COL_LOAD16=1 build and no test reaches it:
-    it is known to compile (124 / 126 VGPRs, no scratch), not to run."""
+    tests/test_gpu_columns.py binds them): COLS 1, 8-B loads."""
     c = forced(1)
     run(c, seq_r(4), zipf_s(1.05), params(), expect_zipf(4, 1.05), columns=True)
     assert c.relation_info(S_).packed == 0
