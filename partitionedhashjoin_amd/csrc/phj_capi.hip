@@ -456,6 +456,31 @@ void reset_timers(phj_ctx* c) {
     if (c->split.p) (void)hipMemsetAsync(c->split.p, 0, 16, c->ks);
 }
 
+// What every entry point that launches work does once its arguments are
+// checked: a stale error left by code outside this library is dropped, the
+// device selected, and the per-call state set: the timer flags of this call
+// (PHJ_DEFER_TIMERS / PHJ_LEAN_TIMERS of phj_join's params, else none), no open
+// timer, no pinned count of an earlier join, launches on the ctx stream.
+// Timers: reset, unless this call defers them or (accumulate: phj_partition
+// and the calls over its output, which report them together) adds to them;
+// a caller that never reports loses the oldest records.
+// Every such entry point clears all of it: before they shared this prologue,
+// phj_join_materialize, phj_probe_pass1, phj_partition, phj_join_partitioned(_async)
+// and phj_relation_count_in_range left count_pinned and timer_skipped (and the
+// last three the timer flags) as the call before them had, so that after an LDS
+// join that failed between its probe and get_count they read that join's pinned count.
+int begin_call(phj_ctx* c, uint32_t timer_flags = 0, bool accumulate = false) {
+    (void)hipGetLastError();
+    PHJ_HIP(c, hipSetDevice(c->device));
+    c->defer_timers = (timer_flags & PHJ_DEFER_TIMERS) != 0;
+    c->lean_timers = (timer_flags & PHJ_LEAN_TIMERS) != 0;
+    c->timer_skipped = false;
+    c->count_pinned = false;
+    c->ks = c->stream;
+    if (!(accumulate || c->defer_timers) || c->timers.size() > kMaxTimerRecs) reset_timers(c);
+    return PHJ_OK;
+}
+
 // Build share of the fused join launches since the last reset (wave clocks).
 double fused_build_fraction(phj_ctx* c) {
     unsigned long long cyc[2] = {0, 0};
@@ -565,7 +590,7 @@ int make_plan(phj_ctx* c, const phj_join_params* p, Plan& pl) {
 // and partition on the refined q in two balanced passes. The count is the
 // same (a partition's hash table is simply organised by further hash bits);
 // phj_partition keeps the exact layout of the requested partitions.
-void refine_plan_sub(const phj_ctx* c, Plan& pl, uint64_t nR) {
+void refine_plan(const phj_ctx* c, Plan& pl, uint64_t nR) {
     if (!c->tune.subpart || !c->tune.fused || pl.P == 0) return;
     const double expect = static_cast<double>(nR) / static_cast<double>(pl.P);
     if (expect * 3 <= static_cast<double>(kFusedTcap) * 2) return;
@@ -590,12 +615,10 @@ void refine_plan_sub(const phj_ctx* c, Plan& pl, uint64_t nR) {
     pl.Ppad = pl.nb1 * pl.nb2;
 }
 
-void refine_plan(const phj_ctx* c, Plan& pl, uint64_t nR) { refine_plan_sub(c, pl, nR); }
-
 // The LDS join's plan (phj_cluster.h) from the requested one (make_plan):
 // pass 1 partitions into K = 2^k clusters, the top k bits of the partition
 // number q (refined by sub-partition bits when q has fewer than k bits: hash
-// bits just above the radix bits, or bits 40+ under h % P, as refine_plan_sub),
+// bits just above the radix bits, or bits 40+ under h % P, as refine_plan),
 // so every cluster is a union of whole requested partitions. K is the smallest
 // power of two >= 256 (chains enough for S's pass-1 cursors) whose average
 // cluster fills at most 0.8 of the LDS limit (the binomial spread of the
@@ -761,6 +784,17 @@ int occupancy(const void* kfn, int block, size_t lds) {
     return occ;
 }
 
+// ... or `fallback` where the runtime cannot tell.
+int occupancy_or(const void* kfn, int block, size_t lds, int fallback) {
+    const int occ = occupancy(kfn, block, lds);
+    return occ < 1 ? fallback : occ;
+}
+
+// A grid of `want` workgroups, at most per_cu on every CU, at least one.
+uint32_t chip_grid(const phj_ctx* c, uint64_t want, int per_cu) {
+    return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want, static_cast<uint64_t>(per_cu) * c->num_cus)));
+}
+
 // ROWS (pass 1 of the row-number joins, phj_index.h): 0 = the payloads are
 // loaded; 1 / 2 = the input is a key column / 16-B tuples whose payloads are
 // ignored, and the payload written is the tuple's row number. Only the passes
@@ -851,7 +885,7 @@ int launch_pass_t(phj_ctx* c, int hk, const PassArgs& a, uint32_t grid, const st
             if (c->p1_cols && !cols_form) return set_err(c, PHJ_ERR_STATE, "key column: this code pass has no column form");
             // workgroups per CU: what the LDS and the kernel's registers allow
             // (cached per kernel and LDS size; one cache per worker thread)
-            const int occ = std::max(1, occupancy(kfn, kblock, lds));
+            const int occ = occupancy_or(kfn, kblock, lds, 1);
             const uint32_t fit = std::max<uint32_t>(1, std::min<uint32_t>(static_cast<uint32_t>(occ), static_cast<uint32_t>(160 * 1024 / lds)));
             uint32_t slots = std::max<uint32_t>(1, std::min<uint32_t>(per, fit * c->num_cus / a.nshards));
             // keys-only (the on-chip join): PHJ_P1_WPC2 half-workgroups per CU, not
@@ -1390,11 +1424,7 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
         const void* kfn = with_hash(pl.hk, [](auto h) {
             return reinterpret_cast<const void*>(&k_join_fused<decltype(h)::value, kFusedKPL, kFusedTcap>);
         });
-        int per_cu = 0;
-        if ((per_cu = occupancy(kfn, kBlock, 0)) < 1) per_cu = 2;
-        const size_t wblocks = (nslots + kWaves - 1) / kWaves;
-        const uint32_t grid = static_cast<uint32_t>(
-            std::max<size_t>(1, std::min<size_t>(wblocks, static_cast<size_t>(per_cu) * c->num_cus)));
+        const uint32_t grid = chip_grid(c, (nslots + kWaves - 1) / kWaves, occupancy_or(kfn, kBlock, 0, 2));
         void* kargs[] = {&fa};
         PHJ_HIP(c, hipLaunchKernel(kfn, dim3(grid), dim3(kBlock), kargs, 0, c->ks));
         PHJ_LAUNCHED(c, "k_join_fused");
@@ -1555,11 +1585,8 @@ int build_and_probe(phj_ctx* c, const Plan& pl, int nseg, const phj_partitioned*
              : small      ? reinterpret_cast<const void*>(&k_probe<HK, 8, 2>)
                           : reinterpret_cast<const void*>(&k_probe<HK, 8, 8>);
     });
-    int per_cu = 0;
-    if ((per_cu = occupancy(kfn, kBlock, 0)) < 1) per_cu = 2;
     const size_t item_blocks = wave_probe ? (item_bound + kWaves - 1) / kWaves : item_bound;
-    const uint32_t pgrid = static_cast<uint32_t>(
-        std::max<size_t>(1, std::min<size_t>(item_blocks, static_cast<size_t>(per_cu) * c->num_cus)));
+    const uint32_t pgrid = chip_grid(c, item_blocks, occupancy_or(kfn, kBlock, 0, 2));
     void* kargs[] = {&pa};
     PHJ_HIP(c, hipLaunchKernel(kfn, dim3(pgrid), dim3(kBlock), kargs, 0, c->ks));
     PHJ_LAUNCHED(c, "k_probe");
@@ -1714,6 +1741,18 @@ bool use_cluster(const phj_ctx* c, const Plan& pl, uint64_t nS, uint64_t nR, Pla
     return cluster_empty0(out) != 0 && 4 * nR + 2ull * out.nb1 < (1ull << 32);
 }
 
+// The counting path a radix join of nS probe and nR build tuples takes on one
+// device, and the plan that path runs: the LDS join on its cluster plan, else,
+// on the plan refined by sub-partitions, the code tables or both sides fully
+// partitioned. phj_join runs it, phj_prepare sizes it, phj_join_path reports
+// it, phj_probe_pass1 shows its pass 1: one decision.
+int radix_path(const phj_ctx* c, const Plan& asked, uint64_t nS, uint64_t nR, Plan& run) {
+    if (use_cluster(c, asked, nS, nR, run)) return PHJ_PATH_LDS_JOIN;
+    run = asked;
+    refine_plan(c, run, nR);
+    return use_p2probe(c, run, nS, nR) ? PHJ_PATH_CODE_TABLES : PHJ_PATH_PARTITIONED;
+}
+
 // Probe a probe-side pass-1 output (partition_state p1_only) against the
 // tables of build_ht; the count lands in (clear) or is added to c->count.
 int probe_ht(phj_ctx* c, const Plan& pl, SideState& PS, bool clear = true) {
@@ -1743,9 +1782,7 @@ int probe_ht(phj_ctx* c, const Plan& pl, SideState& PS, bool clear = true) {
                         });
     // persistent: as many workgroups as fit the chip at once (a multiple of 8:
     // XCD x owns tiles [x, x + 1) * ntiles / 8), never many more than tiles
-    int per_cu = 0;
-    if ((per_cu = occupancy(kfn, B, lds)) < 1) per_cu = 2;
-    per_cu = std::min<int>(per_cu, static_cast<int>(160 * 1024 / lds));
+    const int per_cu = std::min<int>(occupancy_or(kfn, B, lds, 2), static_cast<int>(160 * 1024 / lds));
     const uint32_t want = (PS.nt2 + 7) & ~7u;
     const uint32_t grid = std::max<uint32_t>(8, std::min<uint32_t>(want, static_cast<uint32_t>(per_cu) * c->num_cus) & ~7u);
     void* kargs[] = {&pa};
@@ -1899,9 +1936,7 @@ int probe_cluster(phj_ctx* c, const Plan& pl, SideState& PS, int nseg, const int
     const void* kfn = !RT          ? reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, false>)
                       : a.hot_code ? reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, true, true>)
                                    : reinterpret_cast<const void*>(&k_cluster_probe<B, I, 3, true, PR, true>);
-    int per_cu = 0;
-    if ((per_cu = occupancy(kfn, B, lds)) < 1) per_cu = 1;
-    per_cu = std::max(1, std::min<int>(per_cu, static_cast<int>(160 * 1024 / (lds + 256))));
+    const int per_cu = std::max(1, std::min<int>(occupancy_or(kfn, B, lds, 1), static_cast<int>(160 * 1024 / (lds + 256))));
     // persistent, a multiple of 8 (XCD-grouped ranges), never many more than tiles
     const uint32_t want = (PS.nt2 + 7) & ~7u;
     const uint32_t grid = std::max<uint32_t>(8, std::min<uint32_t>(want, static_cast<uint32_t>(per_cu) * c->num_cus) & ~7u);
@@ -1994,45 +2029,95 @@ int get_count(phj_ctx* c, uint64_t* out, bool pair = false) {
     return check_chunk_errors(c);
 }
 
-// The NoPartitioning count over region code tables (phj_table.h, k_np_probe_ct):
-// R partitioned into 2^k regions of ~300 codes by two radix passes of its hash
-// codes (the build), one code table per region; S probed unpartitioned.
-int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
-    SideState& R = c->side[PHJ_SIDE_BUILD];
-    SideState& S = c->side[PHJ_SIDE_PROBE];
-    uint32_t k = 2;
-    while (k < 22 && (R.n >> k) > 300) k++;
+// R partitioned by the radix bits b0 + b1 of its hash codes under p's hash and
+// seed, whatever else p asks for: the plan of a table build's regions.
+int radix_plan(phj_ctx* c, const phj_join_params* p, uint32_t b0, uint32_t b1, Plan& pl) {
     phj_join_params pp = *p;
     pp.algo = PHJ_ALGO_RADIX;
     pp.num_partitions = 0;
     pp.flags = 0;
-    pp.radix_bits[1] = static_cast<uint8_t>(k / 2);
-    pp.radix_bits[0] = static_cast<uint8_t>(k - k / 2);
+    pp.radix_bits[0] = static_cast<uint8_t>(b0);
+    pp.radix_bits[1] = static_cast<uint8_t>(b1);
+    return make_plan(c, &pp, pl);
+}
+
+// ... into the 2^rbits regions of a bucket table (np_build, index_build): one
+// pass up to 8 bits, beyond two balanced ones.
+int region_plan(phj_ctx* c, const phj_join_params* p, uint32_t rbits, Plan& pl) {
+    const uint32_t b1 = rbits <= 8 ? 0 : rbits / 2;
+    return radix_plan(c, p, rbits - b1, b1, pl);
+}
+
+// The closing of every NoPartitioning form: no partition phase, build = [e0, e1), probe = [e1, e2).
+int np_times(phj_ctx* c, hipEvent_t e0, hipEvent_t e1, hipEvent_t e2, phj_join_result* r) {
+    r->partition_ms = 0;
+    r->build_ms = elapsed(c, e0, e1);
+    r->probe_ms = elapsed(c, e1, e2);
+    r->total_ms = elapsed(c, e0, e2);
+    r->num_partitions = 0;
+    return fill_timers(c, r);
+}
+
+// Region code tables (phj_table.h) over the build side, as the NoPartitioning
+// count and phj_join_member probe them: R partitioned into 2^k regions of ~300
+// codes by two radix passes of its hash codes, one code table per region.
+// marks: a buffer sized to one byte per table slot after the workspace, before
+// the first event (phj_join_member's slot marks), or null.
+// kcol: partition_build's (a side bound as columns is read from its key column).
+// *e0 is recorded before the first kernel. Under phj_prepare (c->dry) only the
+// workspace is sized.
+struct CtBuild {
     Plan pl;
-    PHJ_TRY(make_plan(c, &pp, pl));
-    const uint32_t P = pl.Ppad;
-    const uint64_t slot_bound = 4 * R.n + 2ull * P;
+    uint32_t P = 0;             // regions
+    uint64_t slot_bound = 0;    // table slots
+    const int64_t* rcodes = nullptr;
+    const uint32_t* rbnd = nullptr;
+    uint32_t* uni = nullptr;
+    hipEvent_t e0 = nullptr;
+};
+
+int ct_build(phj_ctx* c, const phj_join_params* p, bool kcol, DevBuf* marks, CtBuild& t) {
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    uint32_t k = 2;
+    while (k < 22 && (R.n >> k) > 300) k++;
+    PHJ_TRY(radix_plan(c, p, k - k / 2, k / 2, t.pl));
+    t.P = t.pl.Ppad;
+    t.slot_bound = 4 * R.n + 2ull * t.P;
     PHJ_TRY(ensure(c, c->r_codes, std::max<uint64_t>(1, R.n) * 8));
-    PHJ_TRY(ensure(c, c->r_bounds, (static_cast<size_t>(P) + 1) * 4));
+    PHJ_TRY(ensure(c, c->r_bounds, (static_cast<size_t>(t.P) + 1) * 4));
     PHJ_TRY(ensure(c, c->np_uni, 16));
     PHJ_TRY(ensure(c, c->count, 32));
-    const int64_t* rcodes = static_cast<const int64_t*>(c->r_codes.p);
-    const uint32_t* rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
-    auto* uni = static_cast<uint32_t*>(c->np_uni.p);
+    if (marks) PHJ_TRY(ensure(c, *marks, t.slot_bound));
+    t.rcodes = static_cast<const int64_t*>(c->r_codes.p);
+    t.rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
+    t.uni = static_cast<uint32_t*>(c->np_uni.p);
     if (c->dry) {
-        PHJ_TRY(partition_build(c, pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p)));
-        return build_ht(c, pl, 1, &rcodes, &rbnd, R.n, uni);
+        PHJ_TRY(partition_build(c, t.pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p), kcol));
+        return build_ht(c, t.pl, 1, &t.rcodes, &t.rbnd, R.n, t.uni);
     }
-    hipEvent_t e0, e1, e2;
-    PHJ_TRY(mark(c, &e0));
+    PHJ_TRY(mark(c, &t.e0));
     // the partition is part of the build (its R.* timers show it)
-    PHJ_TRY(partition_build(c, pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p)));
+    PHJ_TRY(partition_build(c, t.pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p), kcol));
     // algorithmic bytes: the codes read, the tables written (~1.7 slots per code)
     PHJ_TRY(timer_begin(c, "np.build", R.n * 8 * 3));
-    hipLaunchKernelGGL(k_np_ct_plan, dim3(1), dim3(256), 0, c->ks, rbnd, P, slot_bound, uni);
+    hipLaunchKernelGGL(k_np_ct_plan, dim3(1), dim3(256), 0, c->ks, t.rbnd, t.P, t.slot_bound, t.uni);
     PHJ_LAUNCHED(c, "k_np_ct_plan");
-    PHJ_TRY(build_ht(c, pl, 1, &rcodes, &rbnd, R.n, uni));
-    PHJ_TRY(timer_end(c));
+    PHJ_TRY(build_ht(c, t.pl, 1, &t.rcodes, &t.rbnd, R.n, t.uni));
+    return timer_end(c);
+}
+
+// The NoPartitioning count over region code tables (k_np_probe_ct): ct_build
+// (the build), then S probed unpartitioned.
+int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    CtBuild t;
+    PHJ_TRY(ct_build(c, p, false, nullptr, t));
+    if (c->dry) return PHJ_OK;
+    const Plan& pl = t.pl;
+    const uint32_t P = t.P;
+    auto* uni = t.uni;
+    hipEvent_t e1, e2;
     PHJ_TRY(mark(c, &e1));
     PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
     if (S.n > 0) {
@@ -2042,10 +2127,7 @@ int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
         const void* kfn = with_hash(p->hash, [](auto h) {
             return reinterpret_cast<const void*>(&k_np_probe_ct<decltype(h)::value, IT>);
         });
-        int per_cu = 0;
-        if ((per_cu = occupancy(kfn, 256, 0)) < 1) per_cu = 8;
-        const uint64_t want = (S.n + 256ull * IT - 1) / (256ull * IT);
-        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want, static_cast<uint64_t>(per_cu) * c->num_cus)));
+        const uint32_t grid = chip_grid(c, (S.n + 256ull * IT - 1) / (256ull * IT), occupancy_or(kfn, 256, 0, 8));
         const auto* S_rel = reinterpret_cast<const longlong2*>(S.rel);
         const auto* tab = static_cast<const uint64_t*>(c->ht_tab.p);
         const auto* dsc = static_cast<const uint2*>(c->ht_desc.p);
@@ -2063,13 +2145,8 @@ int join_nopart_ct(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     uint64_t m = 0;
     PHJ_TRY(get_count(c, &m));
     r->matches = m;
-    r->partition_ms = 0;
-    r->build_ms = elapsed(c, e0, e1);
-    r->probe_ms = elapsed(c, e1, e2);
-    r->total_ms = elapsed(c, e0, e2);
-    r->num_partitions = 0;
     r->algorithmic_bytes = R.n * (16 + 8 + 8 + 8) + R.n * 24 + S.n * 16 + R.n * 16;
-    return fill_timers(c, r);
+    return np_times(c, t.e0, e1, e2, r);
 }
 
 // phj_join_member (phj_member.h): the build half of join_nopart_ct over keys
@@ -2080,7 +2157,6 @@ int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* p
     const char* what = "phj_join_member";
     if (!c || !r || !n) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
-    (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
     if (sides == 0 || (sides & ~static_cast<uint32_t>(PHJ_MEMBER_PROBE | PHJ_MEMBER_BUILD)))
         return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": sides must be a set of PHJ_MEMBER_PROBE / PHJ_MEMBER_BUILD");
@@ -2099,15 +2175,9 @@ int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* p
     for (const SideState* X : {&R, &S})
         if (!X->rel && !X->columns && X->n > 0) return set_err(c, PHJ_ERR_STATE, "relation not bound");
     if (R.n >= (1ull << 30)) return set_err(c, PHJ_ERR_RANGE, std::string(what) + ": build side of 2^30 rows or more");
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c));
     std::memset(r, 0, sizeof(*r));
     std::memset(n, 0, sizeof(*n));
-    c->defer_timers = false;
-    c->lean_timers = false;
-    c->timer_skipped = false;
-    c->count_pinned = false;
-    c->ks = c->stream;
-    reset_timers(c);
     // an empty side joins to nothing: the other side's mask is all 0, no join runs
     if (R.n == 0 || S.n == 0) {
         if (want_s && S.n > 0) PHJ_HIP(c, hipMemsetAsync(probe_mask, 0, S.n, c->ks));
@@ -2118,35 +2188,14 @@ int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* p
     // keys alone: a side bound as columns is read from its key column, packed or not
     const bool r_keys = R.columns, s_keys = S.columns;
     const uint64_t rk = r_keys ? 8 : 16, sk = s_keys ? 8 : 16;
-    uint32_t k = 2;
-    while (k < 22 && (R.n >> k) > 300) k++;
-    phj_join_params pp = *p;
-    pp.algo = PHJ_ALGO_RADIX;
-    pp.num_partitions = 0;
-    pp.flags = 0;
-    pp.radix_bits[1] = static_cast<uint8_t>(k / 2);
-    pp.radix_bits[0] = static_cast<uint8_t>(k - k / 2);
-    Plan pl;
-    PHJ_TRY(make_plan(c, &pp, pl));
-    const uint32_t P = pl.Ppad;
-    const uint64_t slot_bound = 4 * R.n + 2ull * P;
-    PHJ_TRY(ensure(c, c->r_codes, R.n * 8));
-    PHJ_TRY(ensure(c, c->r_bounds, (static_cast<size_t>(P) + 1) * 4));
-    PHJ_TRY(ensure(c, c->np_uni, 16));
-    PHJ_TRY(ensure(c, c->count, 32));
-    if (want_b) PHJ_TRY(ensure(c, c->member_marks, slot_bound));
-    const int64_t* rcodes = static_cast<const int64_t*>(c->r_codes.p);
-    const uint32_t* rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
-    auto* uni = static_cast<uint32_t*>(c->np_uni.p);
+    CtBuild t;
+    PHJ_TRY(ct_build(c, p, r_keys, want_b ? &c->member_marks : nullptr, t));   // (marks: one byte per table slot)
+    const Plan& pl = t.pl;
+    const uint32_t P = t.P;
+    const uint64_t slot_bound = t.slot_bound;
+    auto* uni = t.uni;
     auto* cnt = static_cast<unsigned long long*>(c->count.p);
-    hipEvent_t e0, e1, e2;
-    PHJ_TRY(mark(c, &e0));
-    PHJ_TRY(partition_build(c, pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p), r_keys));
-    PHJ_TRY(timer_begin(c, "np.build", R.n * 8 * 3));
-    hipLaunchKernelGGL(k_np_ct_plan, dim3(1), dim3(256), 0, c->ks, rbnd, P, slot_bound, uni);
-    PHJ_LAUNCHED(c, "k_np_ct_plan");
-    PHJ_TRY(build_ht(c, pl, 1, &rcodes, &rbnd, R.n, uni));
-    PHJ_TRY(timer_end(c));
+    hipEvent_t e1, e2;
     PHJ_TRY(mark(c, &e1));
     PHJ_HIP(c, hipMemsetAsync(cnt, 0, 32, c->ks));
     const uint64_t per = 256ull * kMemberItems;
@@ -2164,10 +2213,7 @@ int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* p
             return s_keys ? (want_b ? pick(std::true_type{}, std::true_type{}) : pick(std::true_type{}, std::false_type{}))
                           : (want_b ? pick(std::false_type{}, std::true_type{}) : pick(std::false_type{}, std::false_type{}));
         });
-        int per_cu = 0;
-        if ((per_cu = occupancy(kfn, 256, 0)) < 1) per_cu = 8;
-        const uint64_t want = (S.n + per - 1) / per;
-        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want, static_cast<uint64_t>(per_cu) * c->num_cus)));
+        const uint32_t grid = chip_grid(c, (S.n + per - 1) / per, occupancy_or(kfn, 256, 0, 8));
         MemberProbeArgs a{};
         a.keys = s_keys ? S.ckeys : reinterpret_cast<const int64_t*>(S.rel);
         a.n = S.n;
@@ -2192,8 +2238,7 @@ int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* p
             return r_keys ? reinterpret_cast<const void*>(&k_member_build<HK, true>)
                           : reinterpret_cast<const void*>(&k_member_build<HK, false>);
         });
-        const uint64_t want = (R.n + per - 1) / per;
-        const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(want, 8ull * c->num_cus)));
+        const uint32_t grid = chip_grid(c, (R.n + per - 1) / per, 8);
         MemberBuildArgs a{};
         a.keys = r_keys ? R.ckeys : reinterpret_cast<const int64_t*>(R.rel);
         a.n = R.n;
@@ -2218,14 +2263,29 @@ int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* p
     n->probe_matched = h[0];
     n->build_matched = want_b ? h[1] : 0;
     r->matches = h[0];
-    r->partition_ms = 0;
-    r->build_ms = elapsed(c, e0, e1);
-    r->probe_ms = elapsed(c, e1, e2);
-    r->total_ms = elapsed(c, e0, e2);
-    r->num_partitions = 0;
     r->algorithmic_bytes = R.n * (rk + (rk + 8) + 16) + R.n * 24 + S.n * sk + R.n * 16 + (want_s ? S.n : 0) +
                            (want_b ? slot_bound + R.n * (rk + 16 + 1 + 1) : 0);
-    return fill_timers(c, r);
+    return np_times(c, t.e0, e1, e2, r);
+}
+
+// The geometry of a bucket table built by regions (np_build, index_build):
+// `rows` keys at table_ratio (0: the default) slots each in buckets of `slots`,
+// in 2^rbits regions of <= region_buckets buckets (LDS-sized; nbr_max: the most
+// the last doubling may leave a region). what: the prefix of the range message.
+int table_geometry(phj_ctx* c, uint64_t rows, double table_ratio, uint32_t slots, uint32_t region_buckets, uint32_t nbr_max,
+                   const char* what, NPHome& g) {
+    const double ratio = table_ratio > 0 ? table_ratio : kNPDefaultRatio;
+    if (ratio < 1.0) return set_err(c, PHJ_ERR_INVALID, "table_ratio must be >= 1");
+    const double nbd = std::ceil(static_cast<double>(rows) * ratio / slots);
+    if (nbd >= 4294967295.0) return set_err(c, PHJ_ERR_RANGE, std::string(what) + "table too large");
+    const uint32_t nb0 = std::max<uint32_t>(1, static_cast<uint32_t>(nbd));
+    g = NPHome{nb0, nb0, 0, 0};
+    g.rbits = std::min<uint32_t>(22, std::max<uint32_t>(1, ceil_log2((nb0 + region_buckets - 1) / region_buckets)));
+    g.nbr = (nb0 + (1u << g.rbits) - 1) >> g.rbits;
+    const uint64_t nbw = static_cast<uint64_t>(g.nbr) << g.rbits;
+    if (nbw >= 4294967295ull || g.nbr > nbr_max) return set_err(c, PHJ_ERR_RANGE, std::string(what) + "table too large");
+    g.nb = static_cast<uint32_t>(nbw);
+    return PHJ_OK;
 }
 
 // The NoPartitioning bucket table (np_tab, np_pays) over the build side: R
@@ -2237,18 +2297,7 @@ int join_member(phj_ctx* c, const phj_join_params* p, uint32_t sides, uint8_t* p
 // pay: what np_pays holds (PaySrc::RowNumber: each build tuple's row number).
 int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipEvent_t* e0, PaySrc pay = PaySrc::Bound) {
     SideState& R = c->side[PHJ_SIDE_BUILD];
-    const double ratio = p->table_ratio > 0 ? p->table_ratio : kNPDefaultRatio;
-    if (ratio < 1.0) return set_err(c, PHJ_ERR_INVALID, "table_ratio must be >= 1");
-    const double nbd = std::ceil(static_cast<double>(R.n) * ratio / kNPSlots);
-    if (nbd >= 4294967295.0) return set_err(c, PHJ_ERR_RANGE, "table too large");
-    const uint32_t nb0 = std::max<uint32_t>(1, static_cast<uint32_t>(nbd));
-    // region build: 2^rbits regions of <= kNPRegionBuckets buckets (LDS-sized)
-    g = NPHome{nb0, nb0, 0, 0};
-    g.rbits = std::min<uint32_t>(22, std::max<uint32_t>(1, ceil_log2((nb0 + kNPRegionBuckets - 1) / kNPRegionBuckets)));
-    g.nbr = (nb0 + (1u << g.rbits) - 1) >> g.rbits;
-    const uint64_t nbw = static_cast<uint64_t>(g.nbr) << g.rbits;
-    if (nbw >= 4294967295ull || g.nbr > 2 * kNPRegionBuckets) return set_err(c, PHJ_ERR_RANGE, "table too large");
-    g.nb = static_cast<uint32_t>(nbw);
+    PHJ_TRY(table_geometry(c, R.n, p->table_ratio, kNPSlots, kNPRegionBuckets, 2 * kNPRegionBuckets, "", g));
     const uint32_t nb = g.nb;
     // the materialising probe stores a match as the uint32 slot b * 7 + s, and
     // kNoMatch (0xffffffff) must stay out of that range
@@ -2261,16 +2310,8 @@ int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipE
     PHJ_TRY(ensure(c, c->np_ovfb, R.n * 4));
     PHJ_TRY(ensure(c, c->np_ovfn, 4));
     Plan rp;
-    {
-        phj_join_params pp = *p;
-        pp.algo = PHJ_ALGO_RADIX;
-        pp.num_partitions = 0;
-        pp.flags = 0;
-        pp.radix_bits[1] = static_cast<uint8_t>(g.rbits <= 8 ? 0 : g.rbits / 2);
-        pp.radix_bits[0] = static_cast<uint8_t>(g.rbits - pp.radix_bits[1]);
-        PHJ_TRY(make_plan(c, &pp, rp));
-        if (c->dry) return partition_side(c, PHJ_SIDE_BUILD, rp, false, nullptr, pay);
-    }
+    PHJ_TRY(region_plan(c, p, g.rbits, rp));
+    if (c->dry) return partition_side(c, PHJ_SIDE_BUILD, rp, false, nullptr, pay);
     const uint32_t nR = static_cast<uint32_t>(R.n);
     PHJ_TRY(mark(c, e0));
     {
@@ -2298,6 +2339,46 @@ int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipE
     return PHJ_OK;
 }
 
+// The NoPartitioning forms of the inner, row and aggregate joins (one probe of
+// the bucket table over the bound S, four tuples per thread): what they share
+// before their first probe kernel (np_setup) and at their end (np_times), as
+// FusedJoin does for the radix forms.
+struct NPJoin {
+    NPHome g{};
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // around the build
+    uint32_t grid = 0;
+    const longlong2* S_rel = nullptr;
+    const NPBucket* tab = nullptr;
+    const int64_t* pays = nullptr;
+    unsigned long long* cnt = nullptr;
+    uint64_t table_bytes = 0;
+};
+
+// What these forms refuse before they size anything: the hash, 2^32 tuples a side.
+int np_limits(phj_ctx* c, const phj_join_params* p) {
+    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
+        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
+    if (c->side[PHJ_SIDE_BUILD].n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (c->side[PHJ_SIDE_PROBE].n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    return PHJ_OK;
+}
+
+// The table built (np_build), the probe's grid and arguments. Every form calls
+// np_limits itself, before the workspace it sizes ahead of the build, and
+// clears the count word after this if its probe counts there.
+int np_setup(phj_ctx* c, const phj_join_params* p, bool slots32, PaySrc pay, NPJoin& j) {
+    const SideState& S = c->side[PHJ_SIDE_PROBE];
+    PHJ_TRY(np_build(c, p, slots32, j.g, &j.e0, pay));
+    PHJ_TRY(mark(c, &j.e1));
+    j.grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
+    j.S_rel = reinterpret_cast<const longlong2*>(S.rel);
+    j.tab = static_cast<const NPBucket*>(c->np_tab.p);
+    j.pays = static_cast<const int64_t*>(c->np_pays.p);
+    j.cnt = static_cast<unsigned long long*>(c->count.p);
+    j.table_bytes = static_cast<uint64_t>(j.g.nb) * 64;
+    return PHJ_OK;
+}
+
 // phj_index_build (phj_lookup.h): np_build's schedule over buckets of five
 // {code, row} entries. R is partitioned by region with its row numbers as the
 // payload (keys only, nothing packed), one workgroup per region finds or
@@ -2305,19 +2386,9 @@ int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipE
 // the index's own allocation; the partition and the overflow list are the
 // context's workspace and are free again when the call returns.
 int index_geometry(phj_ctx* c, uint64_t rows, double table_ratio, NPHome& g) {
-    const double ratio = table_ratio > 0 ? table_ratio : kNPDefaultRatio;
-    if (ratio < 1.0) return set_err(c, PHJ_ERR_INVALID, "table_ratio must be >= 1");
-    const double nbd = std::ceil(static_cast<double>(std::max<uint64_t>(1, rows)) * ratio / kIxSlots);
-    if (nbd >= 4294967295.0) return set_err(c, PHJ_ERR_RANGE, "phj_index_build: table too large");
-    const uint32_t nb0 = std::max<uint32_t>(1, static_cast<uint32_t>(nbd));
-    g = NPHome{nb0, nb0, 0, 0};
-    g.rbits = std::min<uint32_t>(22, std::max<uint32_t>(1, ceil_log2((nb0 + kIxRegionBuckets - 1) / kIxRegionBuckets)));
-    g.nbr = (nb0 + (1u << g.rbits) - 1) >> g.rbits;
-    const uint64_t nbw = static_cast<uint64_t>(g.nbr) << g.rbits;
     // (a region of more than kIxRegionBuckets buckets would need 2^22 regions of them: beyond 2^32 buckets)
-    if (nbw >= 4294967295ull || g.nbr > kIxRegionBuckets) return set_err(c, PHJ_ERR_RANGE, "phj_index_build: table too large");
-    g.nb = static_cast<uint32_t>(nbw);
-    return PHJ_OK;
+    return table_geometry(c, std::max<uint64_t>(1, rows), table_ratio, kIxSlots, kIxRegionBuckets, kIxRegionBuckets,
+                          "phj_index_build: ", g);
 }
 
 int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index** out, phj_join_result* r) {
@@ -2325,7 +2396,6 @@ int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index*
     if (!c || !out || !r) return PHJ_ERR_INVALID;
     *out = nullptr;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
-    (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
     if (flags & ~static_cast<uint32_t>(PHJ_INDEX_ORDINALS)) return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": unknown flags");
     const bool ordinals = (flags & PHJ_INDEX_ORDINALS) != 0;
@@ -2341,14 +2411,8 @@ int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index*
     if (R.n >= (1ull << 30)) return set_err(c, PHJ_ERR_RANGE, std::string(what) + ": build side of 2^30 rows or more");
     NPHome g{};
     PHJ_TRY(index_geometry(c, R.n, p->table_ratio, g));
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c));
     std::memset(r, 0, sizeof(*r));
-    c->defer_timers = false;
-    c->lean_timers = false;
-    c->timer_skipped = false;
-    c->count_pinned = false;
-    c->ks = c->stream;
-    reset_timers(c);
     const uint32_t nb = g.nb;
     // ordinals: one bit per build row in 32-bit words, rounded to 16 B so that the rank array behind it scans vectorised
     const uint64_t ord_words = ((R.n + 31) / 32 + 3) & ~3ull;
@@ -2391,21 +2455,21 @@ int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index*
     auto hip = [&](hipError_t e, const char* call) {
         return e == hipSuccess ? PHJ_OK : set_err(c, PHJ_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
     };
+    auto launched = [&](const char* kernel) {   // PHJ_LAUNCHED, through fail()
+        c->since_ev++;
+        return hip(hipGetLastError(), (std::string("launch ") + kernel).c_str());
+    };
     if (c->poison >= 0)   // (test hook) the region build writes every bucket before anything reads one
         PHJ_IX(hip(hipMemsetAsync(ix->tab, c->poison, ix->bytes, c->ks), "hipMemsetAsync"));
     const void* kfn = with_hash(p->hash, [&](auto h) {
         return reinterpret_cast<const void*>(&k_ix_lookup<decltype(h)::value, 1>);   // (both strides share a resource shape)
     });
-    int per_cu = occupancy(kfn, 256, 0);
-    if (per_cu < 1) per_cu = 4;
-    ix->max_wgs = static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(std::max(1, c->num_cus));
+    ix->max_wgs = static_cast<uint32_t>(occupancy_or(kfn, 256, 0, 4)) * static_cast<uint32_t>(std::max(1, c->num_cus));
     if (ordinals) {
         const void* afn = with_hash(p->hash, [&](auto h) {
             return reinterpret_cast<const void*>(&k_ix_accumulate<decltype(h)::value, 1>);
         });
-        per_cu = occupancy(afn, 256, 0);
-        if (per_cu < 1) per_cu = 4;
-        ix->acc_wgs = static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(std::max(1, c->num_cus));
+        ix->acc_wgs = static_cast<uint32_t>(occupancy_or(afn, 256, 0, 4)) * static_cast<uint32_t>(std::max(1, c->num_cus));
     }
     if (R.n == 0) {   // a valid index over nothing: every bucket empty, every lookup misses
         PHJ_IX(hip(hipMemsetAsync(ix->tab, 0, ix->bytes, c->ks), "hipMemsetAsync"));
@@ -2415,15 +2479,7 @@ int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index*
         return PHJ_OK;
     }
     Plan rp;
-    {
-        phj_join_params pp = *p;
-        pp.algo = PHJ_ALGO_RADIX;
-        pp.num_partitions = 0;
-        pp.flags = 0;
-        pp.radix_bits[1] = static_cast<uint8_t>(g.rbits <= 8 ? 0 : g.rbits / 2);
-        pp.radix_bits[0] = static_cast<uint8_t>(g.rbits - pp.radix_bits[1]);
-        PHJ_IX(make_plan(c, &pp, rp));
-    }
+    PHJ_IX(region_plan(c, p, g.rbits, rp));
     hipEvent_t e0, e1;
     PHJ_IX(mark(c, &e0));
     PHJ_IX(partition_side(c, PHJ_SIDE_BUILD, rp, false, nullptr, PaySrc::RowNumber));
@@ -2443,11 +2499,9 @@ int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index*
             hipLaunchKernelGGL((k_ix_build_region<decltype(h)::value>), dim3(1u << g.rbits), dim3(kBlock), lds, c->ks, v.keys,
                                v.payloads, v.bounds, g, tab, p->hash_seed, ovn, ov, ovb, cnt);
         });
-        c->since_ev++;
-        PHJ_IX(hip(hipGetLastError(), "launch k_ix_build_region"));
+        PHJ_IX(launched("k_ix_build_region"));
         hipLaunchKernelGGL(k_ix_build_overflow, dim3(64), dim3(kBlock), 0, c->ks, ovn, ov, ovb, tab, nb, cnt);
-        c->since_ev++;
-        PHJ_IX(hip(hipGetLastError(), "launch k_ix_build_overflow"));
+        PHJ_IX(launched("k_ix_build_overflow"));
     }
     PHJ_IX(timer_end(c));
     if (!ordinals) PHJ_IX(mark(c, &e1));
@@ -2478,19 +2532,15 @@ int index_build(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_index*
         PHJ_IX(hip(hipMemsetAsync(bitmap, 0, static_cast<size_t>(words) * 4, c->ks), "hipMemsetAsync"));
         const uint32_t sgrid = static_cast<uint32_t>((static_cast<uint64_t>(nb) * 8 + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(k_ix_ord_mark, dim3(sgrid), dim3(kBlock), 0, c->ks, ix->tab, nb, rows, bitmap);
-        c->since_ev++;
-        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_mark"));
+        PHJ_IX(launched("k_ix_ord_mark"));
         hipLaunchKernelGGL(k_ix_ord_popc, dim3((words + kBlock - 1) / kBlock), dim3(kBlock), 0, c->ks, bitmap, words, rank);
-        c->since_ev++;
-        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_popc"));
+        PHJ_IX(launched("k_ix_ord_popc"));
         PHJ_IX(scan_u32(c, rank, words, 1, words));
         hipLaunchKernelGGL(k_ix_ord_first, dim3((rows + kBlock - 1) / kBlock), dim3(kBlock), 0, c->ks, bitmap, rank, rows,
                            ix->first_rows, distinct);
-        c->since_ev++;
-        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_first"));
+        PHJ_IX(launched("k_ix_ord_first"));
         hipLaunchKernelGGL(k_ix_ord_apply, dim3(sgrid), dim3(kBlock), 0, c->ks, ix->tab, nb, rows, bitmap, rank);
-        c->since_ev++;
-        PHJ_IX(hip(hipGetLastError(), "launch k_ix_ord_apply"));
+        PHJ_IX(launched("k_ix_ord_apply"));
         PHJ_IX(timer_end(c));
         PHJ_IX(mark(c, &e1));
         PHJ_IX(hip(hipStreamSynchronize(c->ks), "hipStreamSynchronize"));
@@ -2656,13 +2706,8 @@ int join_nopart(phj_ctx* c, const phj_join_params* p, phj_join_result* r, uint32
     uint64_t m = 0;
     PHJ_TRY(get_count(c, &m));
     r->matches = m;
-    r->partition_ms = 0;
-    r->build_ms = elapsed(c, e0, e1);
-    r->probe_ms = elapsed(c, e1, e2);
-    r->total_ms = elapsed(c, e0, e2);
-    r->num_partitions = 0;
     r->algorithmic_bytes = R.n * 32 + S.n * 16 + static_cast<uint64_t>(nb) * 64;
-    return fill_timers(c, r);
+    return np_times(c, e0, e1, e2, r);
 }
 
 int check_side(phj_ctx* c, int side) {
@@ -2793,8 +2838,7 @@ int fused_setup(phj_ctx* c, const phj_join_params* p, const char* what, FusedJoi
     fa.nitems = static_cast<uint32_t>(nslots - 1);
     fa.count = static_cast<unsigned long long*>(c->count.p);
     fa.seed = j.pl.seed;
-    j.grid = static_cast<uint32_t>(
-        std::max<size_t>(1, std::min<size_t>((nslots + kWaves - 1) / kWaves, static_cast<size_t>(4) * c->num_cus)));
+    j.grid = chip_grid(c, (nslots + kWaves - 1) / kWaves, 4);
     return PHJ_OK;
 }
 
@@ -2900,27 +2944,18 @@ int inner_emit(phj_ctx* c, phj_join_result* r, uint64_t nS, uint64_t build_bytes
 int join_nopart_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit) {
     SideState& R = c->side[PHJ_SIDE_BUILD];
     SideState& S = c->side[PHJ_SIDE_PROBE];
-    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
-        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
-    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
-    if (S.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
-    NPHome g{};
-    hipEvent_t e0 = nullptr, e1, e2;
-    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));
-    PHJ_TRY(np_build(c, p, true, g, &e0));
-    PHJ_TRY(mark(c, &e1));
-    PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
-    const auto* S_rel = reinterpret_cast<const longlong2*>(S.rel);
-    const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
-    const auto* pays = static_cast<const int64_t*>(c->np_pays.p);
+    PHJ_TRY(np_limits(c, p));
+    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));   // pairs[]: a word per probe tuple, sized before the build
+    NPJoin j;
+    PHJ_TRY(np_setup(c, p, true, PaySrc::Bound, j));
+    PHJ_HIP(c, hipMemsetAsync(j.cnt, 0, 8, c->ks));
     auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
-    auto* cnt = static_cast<unsigned long long*>(c->count.p);
-    const uint64_t table_bytes = static_cast<uint64_t>(g.nb) * 64;
+    const uint64_t table_bytes = j.table_bytes;
+    hipEvent_t e2;
     auto launch = [&](auto e, JoinedRow* rows, uint32_t nrows) -> int {
         with_hash(p->hash, [&](auto h) {
-            hipLaunchKernelGGL((k_np_inner<decltype(h)::value, decltype(e)::value>), dim3(grid), dim3(kBlock), 0, c->ks,
-                               S_rel, S.n, tab, pays, g, p->hash_seed, pairs, cnt, rows, nrows);
+            hipLaunchKernelGGL((k_np_inner<decltype(h)::value, decltype(e)::value>), dim3(j.grid), dim3(kBlock), 0, c->ks,
+                               j.S_rel, S.n, j.tab, j.pays, j.g, p->hash_seed, pairs, j.cnt, rows, nrows);
         });
         PHJ_LAUNCHED(c, "k_np_inner");
         return PHJ_OK;
@@ -2937,12 +2972,7 @@ int join_nopart_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, 
         PHJ_TRY(inner_emit(c, r, S.n, table_bytes, &e2, [&](JoinedRow* rows) {
             return launch(std::true_type{}, rows, static_cast<uint32_t>(m));
         }));
-    r->partition_ms = 0;
-    r->build_ms = elapsed(c, e0, e1);
-    r->probe_ms = elapsed(c, e1, e2);
-    r->total_ms = elapsed(c, e0, e2);
-    r->num_partitions = 0;
-    return fill_timers(c, r);
+    return np_times(c, j.e0, j.e1, e2, r);
 }
 
 // The radix form: both sides fully partitioned (SoA), then the per-partition
@@ -2984,15 +3014,9 @@ int join_radix_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, b
 int join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit, const char* what) {
     if (!c || !r) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
-    (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c));
     std::memset(r, 0, sizeof(*r));
-    c->defer_timers = false;
-    c->lean_timers = false;
-    c->timer_skipped = false;
-    c->count_pinned = false;
-    reset_timers(c);
     if (emit) c->mat_n = c->idx_n = 0;   // (the index columns of phj_join_indices lie in the same buffer)
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
@@ -3094,45 +3118,31 @@ int agg_passes(phj_ctx* c, uint32_t flags, const AggJob& J, phj_join_result* r, 
 int join_nopart_agg(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_join_result* r, phj_join_totals* t) {
     SideState& R = c->side[PHJ_SIDE_BUILD];
     SideState& S = c->side[PHJ_SIDE_PROBE];
-    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
-        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
-    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
-    if (S.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
-    NPHome g{};
-    hipEvent_t e0 = nullptr, e1, e2;
-    PHJ_TRY(np_build(c, p, true, g, &e0));
-    PHJ_TRY(mark(c, &e1));
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
-    const auto* S_rel = reinterpret_cast<const longlong2*>(S.rel);
-    const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
-    const auto* pays = static_cast<const int64_t*>(c->np_pays.p);
-    const uint64_t table_bytes = static_cast<uint64_t>(g.nb) * 64;
+    NPJoin j;
+    PHJ_TRY(np_limits(c, p));
+    PHJ_TRY(np_setup(c, p, true, PaySrc::Bound, j));   // (no count word to clear: the totals land in agg_res)
+    hipEvent_t e2;
     AggJob J;
-    J.nF = static_cast<uint64_t>(g.nb) * kNPSlots;
-    J.tab = tab;
-    J.rp = pays;
-    J.join_bytes = agg_join_bytes(0, S.n) + table_bytes + R.n * 8;
+    J.nF = static_cast<uint64_t>(j.g.nb) * kNPSlots;
+    J.tab = j.tab;
+    J.rp = j.pays;
+    J.join_bytes = agg_join_bytes(0, S.n) + j.table_bytes + R.n * 8;
     J.join = [&](unsigned long long* res, unsigned long long* acc) -> int {
         with_hash(p->hash, [&](auto h) {
             constexpr int HK = decltype(h)::value;
             if (acc)
-                hipLaunchKernelGGL((k_np_agg<HK, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
+                hipLaunchKernelGGL((k_np_agg<HK, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.S_rel, S.n, j.tab, j.pays, j.g,
                                    p->hash_seed, res, acc, J.nF);
             else
-                hipLaunchKernelGGL((k_np_agg<HK, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
+                hipLaunchKernelGGL((k_np_agg<HK, false>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.S_rel, S.n, j.tab, j.pays, j.g,
                                    p->hash_seed, res, acc, J.nF);
         });
         PHJ_LAUNCHED(c, "k_np_agg");
         return PHJ_OK;
     };
-    r->algorithmic_bytes = R.n * 32 + table_bytes;
+    r->algorithmic_bytes = R.n * 32 + j.table_bytes;
     PHJ_TRY(agg_passes(c, flags, J, r, t, &e2));
-    r->partition_ms = 0;
-    r->build_ms = elapsed(c, e0, e1);
-    r->probe_ms = elapsed(c, e1, e2);
-    r->total_ms = elapsed(c, e0, e2);
-    r->num_partitions = 0;
-    return fill_timers(c, r);
+    return np_times(c, j.e0, j.e1, e2, r);
 }
 
 // The radix form: join_radix_inner's precondition and partitioning.
@@ -3197,19 +3207,13 @@ int join_aggregate(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_joi
     const char* what = "phj_join_aggregate";
     if (!c || !r || !t) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
-    (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
     if ((flags & ~static_cast<uint32_t>(PHJ_AGG_GROUPS | PHJ_AGG_MATCHED_ONLY)) ||
         ((flags & PHJ_AGG_MATCHED_ONLY) && !(flags & PHJ_AGG_GROUPS)))
         return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": flags must be 0, PHJ_AGG_GROUPS or PHJ_AGG_GROUPS | PHJ_AGG_MATCHED_ONLY");
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c));
     std::memset(r, 0, sizeof(*r));
     std::memset(t, 0, sizeof(*t));
-    c->defer_timers = false;
-    c->lean_timers = false;
-    c->timer_skipped = false;
-    c->count_pinned = false;
-    reset_timers(c);
     c->agg_n = 0;
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
@@ -3388,24 +3392,21 @@ int join_nopart_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int
                      phj_join_result* r, phj_row_counts* n, bool index = false) {
     SideState& R = c->side[PHJ_SIDE_BUILD];
     SideState& S = c->side[PHJ_SIDE_PROBE];
-    if (p->hash != PHJ_HASH_XXH3 && p->hash != PHJ_HASH_MURMUR3)
-        return set_err(c, PHJ_ERR_INVALID, "unknown hash function");
-    if (R.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
-    if (S.n >= (1ull << 32)) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
-    NPHome g{};
-    hipEvent_t e0 = nullptr, e1, e2;
-    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));
-    PHJ_TRY(ensure(c, c->count, 32));
-    PHJ_TRY(np_build(c, p, true, g, &e0, index ? PaySrc::RowNumber : PaySrc::Bound));
-    PHJ_TRY(mark(c, &e1));
-    PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((S.n + 4 * kBlock - 1) / (4 * kBlock), 8192));
+    PHJ_TRY(np_limits(c, p));
+    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));   // pairs[]: a word per probe tuple, sized before the build
+    PHJ_TRY(ensure(c, c->count, 32));           // {pairs, probe_only, build_only}
+    NPJoin j;
+    PHJ_TRY(np_setup(c, p, true, index ? PaySrc::RowNumber : PaySrc::Bound, j));
+    PHJ_HIP(c, hipMemsetAsync(j.cnt, 0, 8, c->ks));
+    const NPHome& g = j.g;
+    const uint32_t grid = j.grid;
     const bool kcol = index && S.columns;   // the probe side's key column itself
-    const auto* S_rel = kcol ? reinterpret_cast<const longlong2*>(S.ckeys) : reinterpret_cast<const longlong2*>(S.rel);
-    const auto* tab = static_cast<const NPBucket*>(c->np_tab.p);
-    const auto* pays = static_cast<const int64_t*>(c->np_pays.p);
+    const auto* S_rel = kcol ? reinterpret_cast<const longlong2*>(S.ckeys) : j.S_rel;
+    const auto* tab = j.tab;
+    const auto* pays = j.pays;
     auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
-    auto* cnt = static_cast<unsigned long long*>(c->count.p);
+    auto* cnt = j.cnt;
+    hipEvent_t e2;
     RowsJob J;
     J.nS = S.n;
     J.s_aos = index ? nullptr : S_rel;
@@ -3462,12 +3463,7 @@ int join_nopart_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int
     };
     r->algorithmic_bytes = R.n * 32 + J.table_bytes;
     PHJ_TRY(rows_passes(c, classes, null_payload, emit, J, r, n, &e2));
-    r->partition_ms = 0;
-    r->build_ms = elapsed(c, e0, e1);
-    r->probe_ms = elapsed(c, e1, e2);
-    r->total_ms = elapsed(c, e0, e2);
-    r->num_partitions = 0;
-    return fill_timers(c, r);
+    return np_times(c, j.e0, j.e1, e2, r);
 }
 
 // index (phj_join_indices): both sides' pass 1 synthesises row numbers, and
@@ -3575,19 +3571,13 @@ int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t nu
               phj_row_counts* n, bool emit, const char* what, bool index = false) {
     if (!c || !r || !n) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
-    (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
     constexpr uint32_t all = PHJ_ROWS_PAIRS | PHJ_ROWS_PROBE_ONLY | PHJ_ROWS_BUILD_ONLY;
     if (classes == 0 || (classes & ~all))
         return set_err(c, PHJ_ERR_INVALID, std::string(what) + ": classes must be a non-empty set of PHJ_ROWS_*");
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c));
     std::memset(r, 0, sizeof(*r));
     std::memset(n, 0, sizeof(*n));
-    c->defer_timers = false;
-    c->lean_timers = false;
-    c->timer_skipped = false;
-    c->count_pinned = false;
-    reset_timers(c);
     if (emit) c->mat_n = c->idx_n = 0;   // one result at a time
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
@@ -3678,6 +3668,262 @@ int on_solo(phj_ctx* c, const char* what, F f) {
     return rc;
 }
 
+// ---- phj_join's three radix paths (radix_path), each from the plan it runs ----
+// requested: the partitions asked for, as the result reports them.
+
+// PHJ_PATH_LDS_JOIN (phj_cluster.h). cpl: the cluster plan.
+int join_lds(phj_ctx* c, const Plan& cpl, uint32_t requested, phj_join_result* r) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    hipEvent_t t0, t1, tr, b0, p1;
+    // a side bound as columns: its code pass reads the key column where it
+    // has the column form (cols_native), else the side is packed first
+    const bool s_cols = cols_native(c, S, cpl, false), r_cols = cols_native(c, R, cpl, true);
+    if (!r_cols) PHJ_TRY(need_tuples(c, PHJ_SIDE_BUILD, false, "phj_join"));
+    if (!s_cols) PHJ_TRY(need_tuples(c, PHJ_SIDE_PROBE, false, "phj_join"));
+    // the LDS join (phj_cluster.h): S's pass 1 into clusters (codes) on
+    // the main stream; R's pass 1 and the big clusters' HBM tables on the
+    // aux stream beside it; then the probe builds each cluster's table in
+    // LDS and probes S's codes against it
+    PHJ_TRY(ensure(c, c->count, 32));
+    // the result's phase marks: with deferred timers nothing reads them
+    // (the result's phase times stay zero) and, R's chain on the main
+    // stream, no stream waits on them: not recorded (each event between
+    // two kernels delays the second by ~4 us)
+    const int order = c->tune.r_order;
+    const bool r_main = order == 1;
+    const bool no_marks = c->defer_timers && r_main;
+    t0 = tr = b0 = t1 = p1 = nullptr;
+    auto phase_mark = [&](hipEvent_t* e) -> int { return no_marks ? PHJ_OK : mark_shared(c, e); };
+    if (!no_marks) PHJ_TRY(mark(c, &t0));
+    const int64_t* rcodes = nullptr;
+    const uint32_t* rbnd = nullptr;
+    // R's chain on the aux stream, after event `after`
+    // R in tile mode (PHJ_R_CHUNK, default): R through the chunked code
+    // pass as S (one launch; 8 shards, so a cluster below the LDS limit
+    // has at most 8 + 3 runs), its tiles read by the builds; else the
+    // stable pass (k_hist + scan + k_scatter_codes: codes contiguous per cluster)
+    SideState* RT = nullptr;
+    // after S's pass (PHJ_R_ORDER=1, default) R's chain runs on the main
+    // stream itself: nothing runs beside it, and a cross-stream event wait
+    // before the probe costs ~15 us (measured gap, r05z timeline)
+    // with the hot-key pre-aggregation (phj_hot.h): R's
+    // chain on the aux stream from the join's start, beside the hot-key
+    // prologue (a few narrow kernels bound by atomics), its pass 1 leaving
+    // the prologue PHJ_HOT_FREE_CUS CUs per shard; the main stream waits
+    // for it before the LDS join. R's chain reads nothing of S's: the
+    // weights are resolved by the LDS join, not by R's pass
+    const bool hot = hot_wanted(c, cpl, S.n, R.n);
+    const bool early_r = hot && R.n > 0;
+    auto r_chain = [&](hipEvent_t after) -> int {
+        if (!r_main || early_r) {
+            PHJ_HIP(c, hipStreamWaitEvent(c->aux, after, 0));
+            c->ks = c->aux;
+        }
+        int rc = PHJ_OK;
+        if (c->tune.r_chunk && R.n > 0) {
+            c->p1_free_cus = early_r ? PHJ_HOT_FREE_CUS : 0;
+            rc = partition_state(c, R, "R", cpl, true, nullptr, 8);
+            c->p1_free_cus = 0;
+            if (rc == PHJ_OK && R.hcoded) RT = &R;
+        }
+        if (!RT) {
+            if (rc == PHJ_OK) rc = ensure(c, c->r_codes, std::max<uint64_t>(1, R.n) * 8);
+            if (rc == PHJ_OK) rc = ensure(c, c->r_bounds, (static_cast<size_t>(cpl.nb1) + 1) * 4);
+            rcodes = static_cast<const int64_t*>(c->r_codes.p);
+            rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
+            if (rc == PHJ_OK) rc = partition_build(c, cpl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p));
+        }
+        if (rc == PHJ_OK) rc = phase_mark(&b0);
+        // the HBM tables of clusters beyond the LDS limit (none at the
+        // balanced configurations; the LDS tables are built inside the probe)
+        if (rc == PHJ_OK) rc = timer_begin(c, "build.big", 0);
+        if (rc == PHJ_OK) rc = cluster_big_fill(c, cpl, 1, &rcodes, &rbnd, R.n, RT);
+        if (rc == PHJ_OK) rc = timer_end(c);
+        if (rc == PHJ_OK) rc = phase_mark(&tr);
+        c->ks = c->stream;
+        return rc;
+    };
+    // PHJ_R_ORDER: 0 = R's chain beside S's pass 1 (it waits for t0: the
+    // previous step's probe read R's codes), 1 = after S's pass 1, 2 = before it
+    if (order == 2) {
+        PHJ_TRY(r_chain(t0));
+        PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
+    }
+    // the code pass's bookkeeping kernel clears the count pair (an empty
+    // S takes no chunked pass: a memset). R's chain after S's pass on the
+    // same stream: S's bookkeeping kernel also clears R's chunk state (one
+    // memset launch and its gap fewer before R's pass; not with R's chain
+    // ahead of S's pass: its state is in use by then, cleared by a memset
+    // on the aux stream ahead of R's pass)
+    const bool pre_clear = r_main && !early_r && c->tune.r_chunk && R.n > 0 && !c->dry;
+    if (pre_clear) {
+        PHJ_TRY(ensure(c, R.ccur, chunk_state_bytes(cpl.nb1)));
+        c->p1_clear = R.ccur.p;
+        c->p1_clear_bytes = chunk_state_bytes(cpl.nb1);
+    }
+    if (early_r) {
+        // the fork, before the prologue: the previous join's probe
+        // read R's pool and tile list
+        for (hipEvent_t* e : {&c->hot_fork, &c->hot_join})
+            if (!*e && !(*e = new_event())) return set_err(c, PHJ_ERR_HIP, "hipEventCreate failed");
+        PHJ_HIP(c, hipEventRecord(c->hot_fork, c->stream));
+    }
+    // hot probe keys (phj_hot.h): sampled and selected here; S's pass then
+    // counts them instead of writing them, the LDS join looks them up in
+    // the tables it builds and adds the weights of those R holds to the
+    // count (after S's bookkeeping kernel has cleared it: one stream)
+    struct HotScope {
+        phj_ctx* c;
+        bool ok = false;   // the join ran to its end (else the hot state is cleared before its next use)
+        ~HotScope() {
+            c->hot_on = false;
+            if (!ok) c->hot_clean = nullptr;
+        }
+    } hot_scope{c};
+    if (hot) PHJ_TRY(hot_begin(c, cpl, S));
+    if (early_r) {
+        // issued after the prologue's launches (the main stream is the
+        // step's critical path: each launch is a few us of host time) and
+        // ahead of S's pass, which is not held back by it: the workgroups
+        // of S's pass whose CUs R still holds start when R's pass ends
+        int rc = r_chain(c->hot_fork);
+        if (rc == PHJ_OK && hipEventRecord(c->hot_join, c->aux) != hipSuccess) rc = set_err(c, PHJ_ERR_HIP, "hipEventRecord failed");
+        PHJ_TRY(rc);
+    }
+    const int prc = partition_side(c, PHJ_SIDE_PROBE, cpl, true, static_cast<unsigned long long*>(c->count.p));
+    c->p1_clear = nullptr;
+    if (prc != PHJ_OK) {
+        c->p1_cleared = nullptr;
+        return prc;
+    }
+    if (!S.hcoded) PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 32, c->stream));
+    if (order != 2 && !early_r) {
+        const int rc = r_chain(t0);
+        c->p1_cleared = nullptr;   // (R's pass may not have taken the chunked form)
+        PHJ_TRY(rc);
+    }
+    if (!r_main) PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
+    if (early_r) PHJ_HIP(c, hipStreamWaitEvent(c->stream, c->hot_join, 0));
+    if (c->hot_on && R.n > 0 && !RT) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs R's chunked code pass");
+    PHJ_TRY(phase_mark(&t1));
+    // one launch, reported as "build" (the workgroups' table builds in LDS:
+    // R's codes read) and "probe" (S's codes read), split by the kernel's own clocks
+    PHJ_TRY(timer_begin_split(c, R.n * 8, S.n * 8));
+    if (c->lean_timers && c->tune.timers) {   // build.big not timed: a zero-length record keeps the phase listed
+        const hipEvent_t e = c->timers.back().a;
+        c->timers.insert(c->timers.end() - 2, TimerRec{"build.big", 0, e, e});
+    }
+    c->count_pinned = false;
+    PHJ_TRY(probe_cluster(c, cpl, S, 1, &rcodes, &rbnd, RT, true));
+    PHJ_TRY(timer_end_split(c));
+    PHJ_TRY(phase_mark(&p1));
+    uint64_t m = 0;
+    PHJ_TRY(get_count(c, &m, true));
+    r->matches = m;
+    r->partition_ms = elapsed(c, t0, t1);
+    {   // the probe launch split by its clocks (build = the LDS table builds + the big clusters' HBM tables)
+        const double t = elapsed(c, t1, p1), fb = c->tune.timers && !c->defer_timers ? fused_build_fraction(c) : 0.0;
+        r->build_ms = elapsed(c, b0, tr) + t * fb;
+        r->probe_ms = t * (1.0 - fb);
+    }
+    r->total_ms = elapsed(c, t0, p1);
+    r->num_partitions = requested;
+    // R: 16 read + 8 written (pass 1), 8 read (probe); S: 16 read + 8 written, 8 read
+    // (a key column: 8 read in pass 1)
+    r->algorithmic_bytes = R.n * (24 + 8) + S.n * (24 + 8) - (r_cols ? R.n * 8 : 0) - (s_cols ? S.n * 8 : 0);
+    hot_scope.ok = true;
+    return fill_timers(c, r);
+}
+
+// PHJ_PATH_CODE_TABLES (phj_table.h). pl: the refined plan.
+int join_code_tables(phj_ctx* c, const Plan& pl, uint32_t requested, phj_join_result* r) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    hipEvent_t t0, t1, tr, b0, p1;
+    PHJ_TRY(need_tuples_both(c, false, "phj_join"));   // (sides bound as columns: no column form on this path)
+    // S: pass 1 only (its pass 2 runs inside the probe); R: pass 1 as codes
+    // and its tables on the aux stream, beside S (measured: R's chain
+    // issued first, or run before S with S's pass 1 on every LDS slot, is
+    // 0.05-0.1 ms slower; probing S in row ranges, each beside the next
+    // range's pass 1, is 0.3 ms slower: DESIGN.md section 3)
+    PHJ_TRY(ensure(c, c->count, 32));
+    PHJ_TRY(mark(c, &t0));
+    // the code pass's bookkeeping kernel clears the count (hcoded)
+    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl, true, static_cast<unsigned long long*>(c->count.p)));
+    // R's chain waits for t0 (the previous step's probe read its tables);
+    // the wait is issued after S's pass 1 so that launch goes out first
+    PHJ_HIP(c, hipStreamWaitEvent(c->aux, t0, 0));
+    c->ks = c->aux;
+    int rc = ensure(c, c->r_codes, std::max<uint64_t>(1, R.n) * 8);
+    if (rc == PHJ_OK) rc = ensure(c, c->r_bounds, (static_cast<size_t>(pl.Ppad) + 1) * 4);
+    const int64_t* rcodes = static_cast<const int64_t*>(c->r_codes.p);
+    const uint32_t* rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
+    if (rc == PHJ_OK) rc = partition_build(c, pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p));
+    if (rc == PHJ_OK) rc = mark(c, &b0);
+    // algorithmic bytes: the codes read, the tables written (~1.7 slots per code)
+    if (rc == PHJ_OK) rc = timer_begin(c, "build", R.n * 8 * 3);
+    if (rc == PHJ_OK) rc = build_ht(c, pl, 1, &rcodes, &rbnd, R.n);
+    if (rc == PHJ_OK) rc = timer_end(c);
+    if (rc == PHJ_OK) rc = mark(c, &tr);
+    c->ks = c->stream;
+    PHJ_TRY(rc);
+    PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
+    PHJ_TRY(mark(c, &t1));
+    // algorithmic bytes: the pass-1 output read once (16-B tuples, or 8-B
+    // codes after a keys-only pass 1); the tables are re-read from L2
+    PHJ_TRY(timer_begin(c, "probe", S.n * (S.p2.keys_only ? 8 : 16)));
+    PHJ_TRY(probe_ht(c, pl, S, !S.hcoded));
+    PHJ_TRY(timer_end(c));
+    PHJ_TRY(mark(c, &p1));
+    uint64_t m = 0;
+    PHJ_TRY(get_count(c, &m, true));
+    r->matches = m;
+    r->partition_ms = elapsed(c, t0, t1);
+    r->build_ms = elapsed(c, b0, tr);
+    r->probe_ms = elapsed(c, t1, p1);
+    r->total_ms = elapsed(c, t0, p1);
+    r->num_partitions = requested;
+    r->algorithmic_bytes = R.n * (24 + 16) + S.n * (16 + 8) + R.n * 24 + S.n * 8;
+    return fill_timers(c, r);
+}
+
+// PHJ_PATH_PARTITIONED: both sides fully partitioned, then build_and_probe. pl: the refined plan.
+int join_partitioned_sides(phj_ctx* c, const Plan& pl, uint32_t requested, phj_join_result* r) {
+    SideState& R = c->side[PHJ_SIDE_BUILD];
+    SideState& S = c->side[PHJ_SIDE_PROBE];
+    hipEvent_t t0, t1, tr, b0, b1, p1;
+    PHJ_TRY(need_tuples_both(c, false, "phj_join"));   // (sides bound as columns: no column form on this path)
+    // Partition(R) || Partition(S) (HashJoin.hpp:210-216): S (the long one) is
+    // issued first on the ctx stream, R beside it on the aux stream
+    PHJ_TRY(mark(c, &t0));
+    PHJ_HIP(c, hipStreamWaitEvent(c->aux, t0, 0));
+    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl));
+    c->ks = c->aux;
+    int rc = partition_side(c, PHJ_SIDE_BUILD, pl);
+    if (rc == PHJ_OK) rc = mark(c, &tr);
+    c->ks = c->stream;
+    PHJ_TRY(rc);
+    PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
+    PHJ_TRY(mark(c, &t1));
+    PHJ_TRY(build_and_probe(c, pl, 1, &R.view, &b0, &b1, &p1));
+    uint64_t m = 0;
+    PHJ_TRY(get_count(c, &m));
+    r->matches = m;
+    r->partition_ms = elapsed(c, t0, t1);
+    r->build_ms = elapsed(c, b0, b1);
+    r->probe_ms = elapsed(c, b1, p1);
+    if (c->last_fused) {   // one fused launch: split by the kernel's own build / probe clocks
+        const double t = elapsed(c, b0, p1), fb = fused_build_fraction(c);
+        r->build_ms = t * fb;
+        r->probe_ms = t * (1.0 - fb);
+    }
+    r->total_ms = elapsed(c, t0, p1);
+    r->num_partitions = requested;
+    r->algorithmic_bytes = partition_bytes(pl, R.n) + partition_bytes(pl, S.n) + R.n * 32 + S.n * 8 + R.n * 8;
+    return fill_timers(c, r);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3745,11 +3991,9 @@ int phj_join_path(const phj_join_params* p, uint64_t build_n, uint64_t probe_n) 
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) return PHJ_PATH_NO_PARTITIONING;
     if (p->algo != PHJ_ALGO_RADIX) return PHJ_ERR_INVALID;
     phj_ctx tmp;   // default tuning (no device is touched)
-    Plan pl, cpl;
+    Plan pl, run;
     if (make_plan(&tmp, p, pl) != PHJ_OK) return PHJ_ERR_INVALID;
-    if (use_cluster(&tmp, pl, probe_n, build_n, cpl)) return PHJ_PATH_LDS_JOIN;
-    refine_plan(&tmp, pl, build_n);
-    return use_p2probe(&tmp, pl, probe_n, build_n) ? PHJ_PATH_CODE_TABLES : PHJ_PATH_PARTITIONED;
+    return radix_path(&tmp, pl, probe_n, build_n, run);
 }
 
 int phj_exchange_geometry(const phj_join_params* p, uint64_t total_build, uint32_t* num_segments, uint32_t* shift,
@@ -4084,7 +4328,7 @@ int phj_relation_count_in_range(phj_ctx* c, int side, int64_t lo, int64_t hi, ui
         *count = t;
         return PHJ_OK;
     }
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c, 0, true));   // (it records no timer and leaves those of earlier calls)
     SideState& S = c->side[side];
     PHJ_TRY(ensure(c, c->count, 8));
     PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 8, c->ks));
@@ -4105,16 +4349,11 @@ int phj_relation_count_in_range(phj_ctx* c, int side, int64_t lo, int64_t hi, ui
 int phj_partition(phj_ctx* c, int side, const phj_join_params* p, phj_partitioned* out) {
     PHJ_TRY(check_side(c, side));
     if (c->group) return on_solo(c, "phj_partition", [&](phj_ctx* m) { return phj_partition(m, side, p, out); });
-    (void)hipGetLastError();
     if (p && p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "phj_partition needs PHJ_ALGO_RADIX");
     Plan pl;
     PHJ_TRY(make_plan(c, p, pl));
-    PHJ_HIP(c, hipSetDevice(c->device));
-    // timers accumulate until phj_join / phj_join_partitioned / phj_timers_report
-    // reports them; a caller that never reports loses the oldest records
-    c->defer_timers = false;
-    c->lean_timers = false;
-    if (c->timers.size() > kMaxTimerRecs) reset_timers(c);
+    // timers accumulate until phj_join / phj_join_partitioned / phj_timers_report reports them
+    PHJ_TRY(begin_call(c, 0, true));
     PHJ_TRY(need_tuples(c, side, false, "phj_partition"));   // (bound as columns: the payloads of a key column alone are 0)
     PHJ_TRY(partition_side(c, side, pl));
     if (out) *out = c->side[side].view;
@@ -4128,10 +4367,9 @@ int phj_join_partitioned(phj_ctx* c, const phj_join_params* p, int nbuild, const
         return on_solo(c, "phj_join_partitioned", [&](phj_ctx* m) { return phj_join_partitioned(m, p, nbuild, build, r); });
     if (!build) return set_err(c, PHJ_ERR_INVALID, "null build segments");
     if (p && p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "phj_join_partitioned needs PHJ_ALGO_RADIX");
-    (void)hipGetLastError();
     Plan pl;
     PHJ_TRY(make_plan(c, p, pl));
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c, 0, true));   // (with the phj_partition timers since the last report)
     std::memset(r, 0, sizeof(*r));
     hipEvent_t b0, b1, p1;
     PHJ_TRY(build_and_probe(c, pl, nbuild, build, &b0, &b1, &p1));
@@ -4150,8 +4388,6 @@ int phj_join_partitioned(phj_ctx* c, const phj_join_params* p, int nbuild, const
     uint64_t nR = 0;
     for (int g = 0; g < nbuild; g++) nR += build[g].n;
     r->algorithmic_bytes = nR * 32 + c->side[PHJ_SIDE_PROBE].view.n * 8 + nR * 8;
-    c->defer_timers = false;
-    c->lean_timers = false;
     const int rc = fill_timers(c, r);  // includes the phj_partition launches since the last report
     reset_timers(c);
     return rc;
@@ -4166,10 +4402,9 @@ int phj_join_partitioned_async(phj_ctx* c, const phj_join_params* p, int nbuild,
     if (!build || !dev_count) return set_err(c, PHJ_ERR_INVALID, "null build segments or count address");
     if (p && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "phj_join_partitioned_async needs PHJ_ALGO_RADIX");
-    (void)hipGetLastError();
     Plan pl;
     PHJ_TRY(make_plan(c, p, pl));
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c, 0, true));
     hipEvent_t b0, b1, p1;
     PHJ_TRY(build_and_probe(c, pl, nbuild, build, &b0, &b1, &p1));
     PHJ_HIP(c, hipMemcpyAsync(dev_count, c->count.p, 8, hipMemcpyDeviceToDevice, c->ks));
@@ -4178,268 +4413,28 @@ int phj_join_partitioned_async(phj_ctx* c, const phj_join_params* p, int nbuild,
 
 int phj_join(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     if (!c || !r) return PHJ_ERR_INVALID;
-    (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
     if (c->group) {
+        (void)hipGetLastError();   // (the members' calls have no prologue of their own)
         std::memset(r, 0, sizeof(*r));
         return group_join(c, p, r, false);
     }
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c, p->flags));   // (PHJ_DEFER_TIMERS: its timers stay for phj_timers_report)
     std::memset(r, 0, sizeof(*r));
-    c->defer_timers = (p->flags & PHJ_DEFER_TIMERS) != 0;
-    c->lean_timers = (p->flags & PHJ_LEAN_TIMERS) != 0;
-    c->timer_skipped = false;
-    c->count_pinned = false;
     c->hot_ran = false;
-    if (!c->defer_timers || c->timers.size() > kMaxTimerRecs) reset_timers(c);
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) {
         PHJ_TRY(need_tuples_both(c, false, "phj_join"));   // (sides bound as columns)
         return join_nopart(c, p, r);
     }
     if (p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
-    Plan pl;
+    Plan pl, run;
     PHJ_TRY(make_plan(c, p, pl));
-    SideState& R = c->side[PHJ_SIDE_BUILD];
-    SideState& S = c->side[PHJ_SIDE_PROBE];
     const uint32_t requested = pl.Ppad;   // reported; the join may sub-partition
-    hipEvent_t t0, t1, tr, b0, b1, p1;
-    Plan cpl;
-    if (use_cluster(c, pl, S.n, R.n, cpl)) {
-        // a side bound as columns: its code pass reads the key column where it
-        // has the column form (cols_native), else the side is packed first
-        const bool s_cols = cols_native(c, S, cpl, false), r_cols = cols_native(c, R, cpl, true);
-        if (!r_cols) PHJ_TRY(need_tuples(c, PHJ_SIDE_BUILD, false, "phj_join"));
-        if (!s_cols) PHJ_TRY(need_tuples(c, PHJ_SIDE_PROBE, false, "phj_join"));
-        // the LDS join (phj_cluster.h): S's pass 1 into clusters (codes) on
-        // the main stream; R's pass 1 and the big clusters' HBM tables on the
-        // aux stream beside it; then the probe builds each cluster's table in
-        // LDS and probes S's codes against it
-        PHJ_TRY(ensure(c, c->count, 32));
-        // the result's phase marks: with deferred timers nothing reads them
-        // (the result's phase times stay zero) and, R's chain on the main
-        // stream, no stream waits on them: not recorded (each event between
-        // two kernels delays the second by ~4 us)
-        const int order = c->tune.r_order;
-        const bool r_main = order == 1;
-        const bool no_marks = c->defer_timers && r_main;
-        t0 = tr = b0 = t1 = p1 = nullptr;
-        auto phase_mark = [&](hipEvent_t* e) -> int { return no_marks ? PHJ_OK : mark_shared(c, e); };
-        if (!no_marks) PHJ_TRY(mark(c, &t0));
-        const int64_t* rcodes = nullptr;
-        const uint32_t* rbnd = nullptr;
-        // R's chain on the aux stream, after event `after`
-        // R in tile mode (PHJ_R_CHUNK, default): R through the chunked code
-        // pass as S (one launch; 8 shards, so a cluster below the LDS limit
-        // has at most 8 + 3 runs), its tiles read by the builds; else the
-        // stable pass (k_hist + scan + k_scatter_codes: codes contiguous per cluster)
-        SideState* RT = nullptr;
-        // after S's pass (PHJ_R_ORDER=1, default) R's chain runs on the main
-        // stream itself: nothing runs beside it, and a cross-stream event wait
-        // before the probe costs ~15 us (measured gap, r05z timeline)
-        // with the hot-key pre-aggregation (phj_hot.h): R's
-        // chain on the aux stream from the join's start, beside the hot-key
-        // prologue (a few narrow kernels bound by atomics), its pass 1 leaving
-        // the prologue PHJ_HOT_FREE_CUS CUs per shard; the main stream waits
-        // for it before the LDS join. R's chain reads nothing of S's: the
-        // weights are resolved by the LDS join, not by R's pass
-        const bool hot = hot_wanted(c, cpl, S.n, R.n);
-        const bool early_r = hot && R.n > 0;
-        auto r_chain = [&](hipEvent_t after) -> int {
-            if (!r_main || early_r) {
-                PHJ_HIP(c, hipStreamWaitEvent(c->aux, after, 0));
-                c->ks = c->aux;
-            }
-            int rc = PHJ_OK;
-            if (c->tune.r_chunk && R.n > 0) {
-                c->p1_free_cus = early_r ? PHJ_HOT_FREE_CUS : 0;
-                rc = partition_state(c, R, "R", cpl, true, nullptr, 8);
-                c->p1_free_cus = 0;
-                if (rc == PHJ_OK && R.hcoded) RT = &R;
-            }
-            if (!RT) {
-                if (rc == PHJ_OK) rc = ensure(c, c->r_codes, std::max<uint64_t>(1, R.n) * 8);
-                if (rc == PHJ_OK) rc = ensure(c, c->r_bounds, (static_cast<size_t>(cpl.nb1) + 1) * 4);
-                rcodes = static_cast<const int64_t*>(c->r_codes.p);
-                rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
-                if (rc == PHJ_OK) rc = partition_build(c, cpl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p));
-            }
-            if (rc == PHJ_OK) rc = phase_mark(&b0);
-            // the HBM tables of clusters beyond the LDS limit (none at the
-            // balanced configurations; the LDS tables are built inside the probe)
-            if (rc == PHJ_OK) rc = timer_begin(c, "build.big", 0);
-            if (rc == PHJ_OK) rc = cluster_big_fill(c, cpl, 1, &rcodes, &rbnd, R.n, RT);
-            if (rc == PHJ_OK) rc = timer_end(c);
-            if (rc == PHJ_OK) rc = phase_mark(&tr);
-            c->ks = c->stream;
-            return rc;
-        };
-        // PHJ_R_ORDER: 0 = R's chain beside S's pass 1 (it waits for t0: the
-        // previous step's probe read R's codes), 1 = after S's pass 1, 2 = before it
-        if (order == 2) {
-            PHJ_TRY(r_chain(t0));
-            PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
-        }
-        // the code pass's bookkeeping kernel clears the count pair (an empty
-        // S takes no chunked pass: a memset). R's chain after S's pass on the
-        // same stream: S's bookkeeping kernel also clears R's chunk state (one
-        // memset launch and its gap fewer before R's pass; not with R's chain
-        // ahead of S's pass: its state is in use by then, cleared by a memset
-        // on the aux stream ahead of R's pass)
-        const bool pre_clear = r_main && !early_r && c->tune.r_chunk && R.n > 0 && !c->dry;
-        if (pre_clear) {
-            PHJ_TRY(ensure(c, R.ccur, chunk_state_bytes(cpl.nb1)));
-            c->p1_clear = R.ccur.p;
-            c->p1_clear_bytes = chunk_state_bytes(cpl.nb1);
-        }
-        if (early_r) {
-            // the fork, before the prologue: the previous join's probe
-            // read R's pool and tile list
-            for (hipEvent_t* e : {&c->hot_fork, &c->hot_join})
-                if (!*e && !(*e = new_event())) return set_err(c, PHJ_ERR_HIP, "hipEventCreate failed");
-            PHJ_HIP(c, hipEventRecord(c->hot_fork, c->stream));
-        }
-        // hot probe keys (phj_hot.h): sampled and selected here; S's pass then
-        // counts them instead of writing them, the LDS join looks them up in
-        // the tables it builds and adds the weights of those R holds to the
-        // count (after S's bookkeeping kernel has cleared it: one stream)
-        struct HotScope {
-            phj_ctx* c;
-            bool ok = false;   // the join ran to its end (else the hot state is cleared before its next use)
-            ~HotScope() {
-                c->hot_on = false;
-                if (!ok) c->hot_clean = nullptr;
-            }
-        } hot_scope{c};
-        if (hot) PHJ_TRY(hot_begin(c, cpl, S));
-        if (early_r) {
-            // issued after the prologue's launches (the main stream is the
-            // step's critical path: each launch is a few us of host time) and
-            // ahead of S's pass, which is not held back by it: the workgroups
-            // of S's pass whose CUs R still holds start when R's pass ends
-            int rc = r_chain(c->hot_fork);
-            if (rc == PHJ_OK && hipEventRecord(c->hot_join, c->aux) != hipSuccess) rc = set_err(c, PHJ_ERR_HIP, "hipEventRecord failed");
-            PHJ_TRY(rc);
-        }
-        const int prc = partition_side(c, PHJ_SIDE_PROBE, cpl, true, static_cast<unsigned long long*>(c->count.p));
-        c->p1_clear = nullptr;
-        if (prc != PHJ_OK) {
-            c->p1_cleared = nullptr;
-            return prc;
-        }
-        if (!S.hcoded) PHJ_HIP(c, hipMemsetAsync(c->count.p, 0, 32, c->stream));
-        if (order != 2 && !early_r) {
-            const int rc = r_chain(t0);
-            c->p1_cleared = nullptr;   // (R's pass may not have taken the chunked form)
-            PHJ_TRY(rc);
-        }
-        if (!r_main) PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
-        if (early_r) PHJ_HIP(c, hipStreamWaitEvent(c->stream, c->hot_join, 0));
-        if (c->hot_on && R.n > 0 && !RT) return set_err(c, PHJ_ERR_STATE, "hot-key pre-aggregation needs R's chunked code pass");
-        PHJ_TRY(phase_mark(&t1));
-        // one launch, reported as "build" (the workgroups' table builds in LDS:
-        // R's codes read) and "probe" (S's codes read), split by the kernel's own clocks
-        PHJ_TRY(timer_begin_split(c, R.n * 8, S.n * 8));
-        if (c->lean_timers && c->tune.timers) {   // build.big not timed: a zero-length record keeps the phase listed
-            const hipEvent_t e = c->timers.back().a;
-            c->timers.insert(c->timers.end() - 2, TimerRec{"build.big", 0, e, e});
-        }
-        c->count_pinned = false;
-        PHJ_TRY(probe_cluster(c, cpl, S, 1, &rcodes, &rbnd, RT, true));
-        PHJ_TRY(timer_end_split(c));
-        PHJ_TRY(phase_mark(&p1));
-        uint64_t m = 0;
-        PHJ_TRY(get_count(c, &m, true));
-        r->matches = m;
-        r->partition_ms = elapsed(c, t0, t1);
-        {   // the probe launch split by its clocks (build = the LDS table builds + the big clusters' HBM tables)
-            const double t = elapsed(c, t1, p1), fb = c->tune.timers && !c->defer_timers ? fused_build_fraction(c) : 0.0;
-            r->build_ms = elapsed(c, b0, tr) + t * fb;
-            r->probe_ms = t * (1.0 - fb);
-        }
-        r->total_ms = elapsed(c, t0, p1);
-        r->num_partitions = requested;
-        // R: 16 read + 8 written (pass 1), 8 read (probe); S: 16 read + 8 written, 8 read
-        // (a key column: 8 read in pass 1)
-        r->algorithmic_bytes = R.n * (24 + 8) + S.n * (24 + 8) - (r_cols ? R.n * 8 : 0) - (s_cols ? S.n * 8 : 0);
-        hot_scope.ok = true;
-        return fill_timers(c, r);
+    switch (radix_path(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n, run)) {
+        case PHJ_PATH_LDS_JOIN: return join_lds(c, run, requested, r);
+        case PHJ_PATH_CODE_TABLES: return join_code_tables(c, run, requested, r);
+        default: return join_partitioned_sides(c, run, requested, r);
     }
-    PHJ_TRY(need_tuples_both(c, false, "phj_join"));   // (sides bound as columns: no column form on these paths)
-    refine_plan(c, pl, R.n);
-    if (use_p2probe(c, pl, S.n, R.n)) {
-        // S: pass 1 only (its pass 2 runs inside the probe); R: pass 1 as codes
-        // and its tables on the aux stream, beside S (measured: R's chain
-        // issued first, or run before S with S's pass 1 on every LDS slot, is
-        // 0.05-0.1 ms slower; probing S in row ranges, each beside the next
-        // range's pass 1, is 0.3 ms slower: DESIGN.md section 3)
-        PHJ_TRY(ensure(c, c->count, 32));
-        PHJ_TRY(mark(c, &t0));
-        // the code pass's bookkeeping kernel clears the count (hcoded)
-        PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl, true, static_cast<unsigned long long*>(c->count.p)));
-        // R's chain waits for t0 (the previous step's probe read its tables);
-        // the wait is issued after S's pass 1 so that launch goes out first
-        PHJ_HIP(c, hipStreamWaitEvent(c->aux, t0, 0));
-        c->ks = c->aux;
-        int rc = ensure(c, c->r_codes, std::max<uint64_t>(1, R.n) * 8);
-        if (rc == PHJ_OK) rc = ensure(c, c->r_bounds, (static_cast<size_t>(pl.Ppad) + 1) * 4);
-        const int64_t* rcodes = static_cast<const int64_t*>(c->r_codes.p);
-        const uint32_t* rbnd = static_cast<const uint32_t*>(c->r_bounds.p);
-        if (rc == PHJ_OK) rc = partition_build(c, pl, static_cast<int64_t*>(c->r_codes.p), static_cast<uint32_t*>(c->r_bounds.p));
-        if (rc == PHJ_OK) rc = mark(c, &b0);
-        // algorithmic bytes: the codes read, the tables written (~1.7 slots per code)
-        if (rc == PHJ_OK) rc = timer_begin(c, "build", R.n * 8 * 3);
-        if (rc == PHJ_OK) rc = build_ht(c, pl, 1, &rcodes, &rbnd, R.n);
-        if (rc == PHJ_OK) rc = timer_end(c);
-        if (rc == PHJ_OK) rc = mark(c, &tr);
-        c->ks = c->stream;
-        PHJ_TRY(rc);
-        PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
-        PHJ_TRY(mark(c, &t1));
-        // algorithmic bytes: the pass-1 output read once (16-B tuples, or 8-B
-        // codes after a keys-only pass 1); the tables are re-read from L2
-        PHJ_TRY(timer_begin(c, "probe", S.n * (S.p2.keys_only ? 8 : 16)));
-        PHJ_TRY(probe_ht(c, pl, S, !S.hcoded));
-        PHJ_TRY(timer_end(c));
-        PHJ_TRY(mark(c, &p1));
-        uint64_t m = 0;
-        PHJ_TRY(get_count(c, &m, true));
-        r->matches = m;
-        r->partition_ms = elapsed(c, t0, t1);
-        r->build_ms = elapsed(c, b0, tr);
-        r->probe_ms = elapsed(c, t1, p1);
-        r->total_ms = elapsed(c, t0, p1);
-        r->num_partitions = requested;
-        r->algorithmic_bytes = R.n * (24 + 16) + S.n * (16 + 8) + R.n * 24 + S.n * 8;
-        return fill_timers(c, r);
-    }
-    // Partition(R) || Partition(S) (HashJoin.hpp:210-216): S (the long one) is
-    // issued first on the ctx stream, R beside it on the aux stream
-    PHJ_TRY(mark(c, &t0));
-    PHJ_HIP(c, hipStreamWaitEvent(c->aux, t0, 0));
-    PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl));
-    c->ks = c->aux;
-    int rc = partition_side(c, PHJ_SIDE_BUILD, pl);
-    if (rc == PHJ_OK) rc = mark(c, &tr);
-    c->ks = c->stream;
-    PHJ_TRY(rc);
-    PHJ_HIP(c, hipStreamWaitEvent(c->stream, tr, 0));
-    PHJ_TRY(mark(c, &t1));
-    PHJ_TRY(build_and_probe(c, pl, 1, &R.view, &b0, &b1, &p1));
-    uint64_t m = 0;
-    PHJ_TRY(get_count(c, &m));
-    r->matches = m;
-    r->partition_ms = elapsed(c, t0, t1);
-    r->build_ms = elapsed(c, b0, b1);
-    r->probe_ms = elapsed(c, b1, p1);
-    if (c->last_fused) {   // one fused launch: split by the kernel's own build / probe clocks
-        const double t = elapsed(c, b0, p1), fb = fused_build_fraction(c);
-        r->build_ms = t * fb;
-        r->probe_ms = t * (1.0 - fb);
-    }
-    r->total_ms = elapsed(c, t0, p1);
-    r->num_partitions = requested;
-    r->algorithmic_bytes = partition_bytes(pl, R.n) + partition_bytes(pl, S.n) + R.n * 32 + S.n * 8 + R.n * 8;
-    return fill_timers(c, r);
 }
 
 int phj_prepare(phj_ctx* c, const phj_join_params* p) {
@@ -4449,8 +4444,7 @@ int phj_prepare(phj_ctx* c, const phj_join_params* p) {
         phj_join_result r{};
         return group_join(c, p, &r, true);
     }
-    (void)hipGetLastError();
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c, 0, true));   // (no timer is recorded; those of earlier calls stay)
     PHJ_TRY(reserve_events(c, kPrepEvents));
     struct DryScope {
         phj_ctx* c;
@@ -4463,10 +4457,15 @@ int phj_prepare(phj_ctx* c, const phj_join_params* p) {
         return join_nopart(c, p, &r);
     }
     if (p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
-    Plan pl, cpl;
-    PHJ_TRY(make_plan(c, p, pl));
-    if (use_cluster(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n, cpl)) {
-        const uint64_t nR = c->side[PHJ_SIDE_BUILD].n;
+    Plan asked, pl;
+    PHJ_TRY(make_plan(c, p, asked));
+    const uint64_t nR = c->side[PHJ_SIDE_BUILD].n;
+    // the workspace of the path phj_join takes (radix_path), by that path's own
+    // sizing calls; its bodies (join_lds ...) record events, wait across streams
+    // and read the count back, so they are listed here, not run dry
+    const int path = radix_path(c, asked, c->side[PHJ_SIDE_PROBE].n, nR, pl);
+    if (path == PHJ_PATH_LDS_JOIN) {
+        const Plan& cpl = pl;
         // (sides bound as columns: the tuple copy of a side phj_join would pack)
         if (!cols_native(c, c->side[PHJ_SIDE_BUILD], cpl, true)) PHJ_TRY(need_tuples(c, PHJ_SIDE_BUILD, false, "phj_prepare"));
         if (!cols_native(c, c->side[PHJ_SIDE_PROBE], cpl, false)) PHJ_TRY(need_tuples(c, PHJ_SIDE_PROBE, false, "phj_prepare"));
@@ -4480,9 +4479,7 @@ int phj_prepare(phj_ctx* c, const phj_join_params* p) {
         return PHJ_OK;
     }
     PHJ_TRY(need_tuples_both(c, false, "phj_prepare"));
-    refine_plan(c, pl, c->side[PHJ_SIDE_BUILD].n);
-    if (use_p2probe(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n)) {
-        const uint64_t nR = c->side[PHJ_SIDE_BUILD].n;
+    if (path == PHJ_PATH_CODE_TABLES) {
         PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl, true));
         PHJ_TRY(ensure(c, c->r_codes, std::max<uint64_t>(1, nR) * 8));
         PHJ_TRY(ensure(c, c->r_bounds, (static_cast<size_t>(pl.Ppad) + 1) * 4));
@@ -4550,13 +4547,9 @@ static_assert(sizeof(phj_joined) == 24 && sizeof(JoinedRow) == sizeof(phj_joined
 int phj_join_materialize(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
     if (!c || !r) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_join_materialize: single-device contexts only");
-    (void)hipGetLastError();
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
-    PHJ_HIP(c, hipSetDevice(c->device));
+    PHJ_TRY(begin_call(c));
     std::memset(r, 0, sizeof(*r));
-    c->defer_timers = false;
-    c->lean_timers = false;
-    reset_timers(c);
     c->mat_n = c->idx_n = 0;   // (the index columns of phj_join_indices lie in the same buffer)
     PHJ_TRY(need_tuples_both(c, true, "phj_join_materialize"));   // (sides bound as columns)
     if (p->algo == PHJ_ALGO_NO_PARTITIONING) {
@@ -4782,24 +4775,14 @@ int phj_probe_pass1(phj_ctx* c, const phj_join_params* p, int64_t* keys, uint64_
     if (!c) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_probe_pass1 takes a single-device context");
     if (!p || !bounds1 || !nb1 || !codes || (n && !keys)) return set_err(c, PHJ_ERR_INVALID, "null argument");
-    (void)hipGetLastError();
-    PHJ_HIP(c, hipSetDevice(c->device));
     if (p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "radix join parameters required");
     SideState& S = c->side[PHJ_SIDE_PROBE];
     if (n != S.n) return set_err(c, PHJ_ERR_INVALID, "n must be the probe relation's size");
-    Plan pl, cpl;
-    PHJ_TRY(make_plan(c, p, pl));
-    if (use_cluster(c, pl, S.n, c->side[PHJ_SIDE_BUILD].n, cpl)) {
-        pl = cpl;   // phj_join's LDS join: pass 1 into its clusters
-    } else {
-        refine_plan(c, pl, c->side[PHJ_SIDE_BUILD].n);
-        if (!use_p2probe(c, pl, S.n, c->side[PHJ_SIDE_BUILD].n))
-            return set_err(c, PHJ_ERR_STATE, "these params do not take the on-chip probe");
-    }
-    c->defer_timers = false;
-    c->lean_timers = false;
-    reset_timers(c);
-    c->ks = c->stream;
+    Plan asked, pl;   // pl: the LDS join's clusters, or the code tables' plan
+    PHJ_TRY(make_plan(c, p, asked));
+    if (radix_path(c, asked, S.n, c->side[PHJ_SIDE_BUILD].n, pl) == PHJ_PATH_PARTITIONED)
+        return set_err(c, PHJ_ERR_STATE, "these params do not take the on-chip probe");
+    PHJ_TRY(begin_call(c));
     if (!cols_native(c, S, pl, false)) PHJ_TRY(need_tuples(c, PHJ_SIDE_PROBE, false, "phj_probe_pass1"));   // (bound as columns)
     PHJ_TRY(partition_side(c, PHJ_SIDE_PROBE, pl, true));
     const uint32_t nt = S.nt2;
@@ -4830,19 +4813,12 @@ int phj_debug_poison_chunk_table(phj_ctx* c, int side, const phj_join_params* p,
     PHJ_TRY(check_side(c, side));
     if (c->group) return set_err(c, PHJ_ERR_STATE, "phj_debug_poison_chunk_table takes a single-device context");
     if (!p || p->algo != PHJ_ALGO_RADIX) return set_err(c, PHJ_ERR_INVALID, "radix join parameters required");
-    (void)hipGetLastError();
-    PHJ_HIP(c, hipSetDevice(c->device));
-    Plan pl, cpl;
-    PHJ_TRY(make_plan(c, p, pl));
-    bool p1_only;
-    if (use_cluster(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n, cpl)) {
-        pl = cpl;
-        p1_only = side == PHJ_SIDE_PROBE;
-    } else {
-        refine_plan(c, pl, c->side[PHJ_SIDE_BUILD].n);
-        // the pass phj_join runs on this side: keys-only codes for the on-chip probe
-        p1_only = side == PHJ_SIDE_PROBE && use_p2probe(c, pl, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n);
-    }
+    PHJ_TRY(begin_call(c, 0, true));
+    Plan asked, pl;
+    PHJ_TRY(make_plan(c, p, asked));
+    // the pass phj_join runs on this side: keys-only codes for the on-chip probes
+    const bool p1_only = radix_path(c, asked, c->side[PHJ_SIDE_PROBE].n, c->side[PHJ_SIDE_BUILD].n, pl) != PHJ_PATH_PARTITIONED &&
+                         side == PHJ_SIDE_PROBE;
     SideState& S = c->side[side];
     if (!S.ctab.p) {   // no pass has allocated it yet: size it for phj_join's pass
         struct DryScope {

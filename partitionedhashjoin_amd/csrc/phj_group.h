@@ -848,18 +848,17 @@ int group_join(phj_ctx* shell, const phj_join_params* p, phj_join_result* r, boo
     if (p->algo != PHJ_ALGO_RADIX) return set_err(shell, PHJ_ERR_INVALID, "Unrecognized join algorithm");
     if (G.world > kMaxSegs) return set_err(shell, PHJ_ERR_RANGE, "at most 16 ranks");
     Plan pl;
-    // planned with member 0's tuning (refine_plan below uses it too), so a
+    // planned with member 0's tuning (radix_path below uses it too), so a
     // group plans exactly as a single-device context would
     if (const int rc = make_plan(G.mem[0], p, pl); rc != PHJ_OK) return set_err(shell, rc, G.mem[0]->err);
     const uint32_t requested = pl.Ppad;
     // every rank plans for the GLOBAL build side (the gathered segments), so all
     // ranks partition by the same function: the LDS join's clusters, or the
     // code tables' refined plan
-    Plan cpl;
     uint64_t max_s = 0;   // the largest probe shard: every member's S takes the cluster plan's code pass
     for (uint64_t x : G.n[PHJ_SIDE_PROBE]) max_s = std::max(max_s, x);
-    if (use_cluster(G.mem[0], pl, max_s, total(G.n[PHJ_SIDE_BUILD]), cpl)) pl = cpl;
-    else refine_plan(G.mem[0], pl, total(G.n[PHJ_SIDE_BUILD]));
+    const Plan asked = pl;
+    (void)radix_path(G.mem[0], asked, max_s, total(G.n[PHJ_SIDE_BUILD]), pl);   // (each member decides on the code tables from its own shard: member_p2)
     if (dry) return for_members(shell, G, [&](int i) { return member_prepare_radix(G, i, pl); });
     PHJ_TRY(for_members(shell, G, [&](int i) { return member_radix(G, i, pl, &G.res[i]); }));
     merge_results(G, r);

@@ -159,7 +159,7 @@ def partition_of(codes, params, sub_bits=0):
     """csrc/phj_partition.h q_from_hash over uint64 codes: h & (2^k - 1) for
     radix bits, h % P otherwise; refined by sub_bits further bits (the bits
     just above the radix bits, or from bit 40 on: csrc/phj_capi.hip
-    refine_plan_sub)."""
+    refine_plan)."""
     codes = np.asarray(codes, dtype=np.uint64)
     one = np.uint64(1)
     if params.num_partitions > 0:

@@ -55,7 +55,7 @@ def requested_partitions(params):
 
 
 def sub_bits(params, n_build):
-    """csrc/phj_capi.hip refine_plan_sub: the bits a too-coarse plan is refined by."""
+    """csrc/phj_capi.hip refine_plan: the bits a too-coarse plan is refined by."""
     P = requested_partitions(params)
     expect = n_build / P
     if expect * 3 <= TCAP * 2:

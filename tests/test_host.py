@@ -181,3 +181,19 @@ def test_join_path_declines_lds_join_above_the_pool_bound():
     assert phj.join_path(phj.radix_params(num_partitions=1024, hash=phj.HASH_XXH3), nR, 200_000_000) == phj.PATH_LDS_JOIN
     assert phj.join_path(phj.radix_params((8, 8), stable=True), nR, 1000) != phj.PATH_LDS_JOIN
     assert phj.join_path(phj.nopart_params(), nR, 200_000_000) == phj.PATH_NO_PARTITIONING
+
+
+@pytest.mark.parametrize("params,path", [
+    (dict(bits=(8, 8), hash="HASH_MURMUR3"), "PATH_LDS_JOIN"),
+    (dict(num_partitions=32, hash="HASH_XXH3"), "PATH_LDS_JOIN"),
+    (dict(bits=(8, 8), hash="HASH_MURMUR3", stable=True), "PATH_CODE_TABLES"),
+    (dict(bits=(8, 8), hash="HASH_MURMUR3", chained=True), "PATH_PARTITIONED"),
+], ids=["8+8 murmur3", "p32 xxh3", "stable 8+8", "chained 8+8"])
+def test_join_path_at_the_prepare_then_join_sizes(params, path):
+    """phj_join_path at 50 000 x 600 001 (tests/test_gpu_parity.py
+    test_prepare_then_join): the path phj_join, phj_prepare, phj_join_path and
+    phj_probe_pass1 each chose by their own copy of the decision, recorded
+    before the four shared radix_path. Host-only."""
+    import partitionedhashjoin_amd as phj
+    p = phj.radix_params(seed=0x9E3779B97F4A7C15, **dict(params, hash=getattr(phj, params["hash"])))
+    assert phj.join_path(p, 50_000, 600_001) == getattr(phj, path)
