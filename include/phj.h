@@ -149,9 +149,10 @@ typedef struct phj_partitioned {
  * 0 .. ngpus-1), SURVEY.md §8(b). ngpus == 1 gives a single-device context.
  * With ngpus > 1 every relation call takes the whole relation and range-shards
  * it (rank r holds rows [r*n/ngpus, (r+1)*n/ngpus)), and phj_join / phj_prepare
- * run the multi-GPU join with RCCL collectives (at most 16 ranks). This is the
- * reference's Run() with its thread pool (src/main.cpp:235-241, dispatch
- * :260-276) replaced by devices. */
+ * run the multi-GPU join with RCCL collectives (at most 16 ranks: ngpus, or
+ * phj_ctx_create_rank's nranks, outside [1, 16] gives PHJ_ERR_INVALID and no
+ * context). This is the reference's Run() with its thread pool
+ * (src/main.cpp:235-241, dispatch :260-276) replaced by devices. */
 int phj_ctx_create(int ngpus, const int *devs, phj_ctx **out);
 /* flags for phj_ctx_create_ex */
 #define PHJ_CTX_EXCHANGE 0x1 /* take the multi-GPU path even on one device (an RCCL world of one) */
@@ -181,9 +182,11 @@ void phj_shard_range(uint64_t n, int rank, int world, uint64_t *lo, uint64_t *hi
  * exported so that a caller driving its own transport, and the CPU tests over
  * gloo, follow the same layout and reduction:
  *  - the exchange block of one rank (the all-gathered unit, int64 elements):
- *    its build codes in final partition order, zero padded to *codes_elems
- *    (a multiple of 64, >= the largest rank's shard), then the partition bounds
- *    (num_partitions + 1 uint32, two per element), *block_elems in all; a rank
+ *    its build codes in final partition order, then padding up to *codes_elems
+ *    (a multiple of 64, >= the largest rank's shard; the padding's value is
+ *    unspecified, no rank writes it and none reads it: a segment ends at its
+ *    last bound), then the partition bounds (num_partitions + 1 uint32, two
+ *    per element), *block_elems in all; a rank
  *    that failed before the all-gather still takes part with an all-zero
  *    block (bounds all 0: an empty build segment);
  *  - the count all-reduce (sum, uint64): every rank contributes the two words

@@ -78,8 +78,9 @@ def shard_range(n: int, rank: int, world: int):
 
 
 def exchange_layout(max_shard: int, num_partitions: int):
-    """(codes_elems, block_elems) of one rank's exchange block: codes, zero
-    padded, then num_partitions + 1 uint32 bounds (phj_exchange_layout; host only)."""
+    """(codes_elems, block_elems) of one rank's exchange block: codes, padding
+    (unspecified, never read), then num_partitions + 1 uint32 bounds
+    (phj_exchange_layout; host only)."""
     L = _capi.load()
     a, b = C.c_uint64(), C.c_uint64()
     L.phj_exchange_layout(max_shard, num_partitions, C.byref(a), C.byref(b))

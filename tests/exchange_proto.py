@@ -8,6 +8,9 @@ bounds). This module packs a rank's R shard by those rules from the oracle's
 hash codes, reads gathered blocks back as segments, and compares a block
 with another as the protocol allows: bounds exact, each segment's codes the
 same multiset (the device pass leaves the order inside a segment free).
+Params whose join is the fully partitioned one (PHJ_PATH_PARTITIONED, e.g.
+PHJ_TABLE_CHAINED) ship the build KEYS in the same grouping instead of their
+codes: that join hashes them again on the receiving rank.
 """
 import numpy as np
 
@@ -37,15 +40,23 @@ def codes_of(keys, params):
     return O.hash_keys(kind, np.ascontiguousarray(keys, dtype=np.int64), params.hash_seed).view(np.int64)
 
 
+def ships_keys(params, total_build):
+    """Whether the block carries build keys (the fully partitioned join), not codes."""
+    return phj.join_path(params, total_build, 0) == phj.PATH_PARTITIONED
+
+
 def pack(R_shard, params, total_build, codes_elems, block_elems):
-    """This rank's exchange block: its build codes grouped by segment, zero
-    padded to codes_elems, then the num_segments + 1 uint32 bounds."""
+    """This rank's exchange block: its build codes (or keys, ships_keys)
+    grouped by segment, then padding up to codes_elems (zero here; the library
+    leaves it unwritten and never reads it), then the num_segments + 1 uint32
+    bounds."""
     nseg, segment_of = geometry(params, total_build)
-    codes = codes_of(R_shard[:, 0], params)
+    keys = np.ascontiguousarray(R_shard[:, 0], dtype=np.int64)
+    codes = codes_of(keys, params)
     seg = segment_of(codes)
     order = np.argsort(seg, kind="stable")
     block = np.zeros(block_elems, dtype=np.int64)
-    block[:codes.shape[0]] = codes[order]
+    block[:codes.shape[0]] = (keys if ships_keys(params, total_build) else codes)[order]
     bounds = np.zeros(nseg + 1, dtype=np.uint32)
     bounds[1:] = np.cumsum(np.bincount(seg, minlength=nseg))
     block[codes_elems:].view(np.uint32)[:nseg + 1] = bounds
@@ -68,8 +79,10 @@ def same_block(a, b, nseg, codes_elems):
     bb = b[codes_elems:].view(np.uint32)[:nseg + 1]
     if not np.array_equal(ba, bb):
         return False
-    for s in range(nseg):
-        lo, hi = int(ba[s]), int(ba[s + 1])
-        if not np.array_equal(np.sort(a[lo:hi]), np.sort(b[lo:hi])):
-            return False
-    return True
+    sizes = np.diff(ba.astype(np.int64))
+    n = int(ba[nseg])
+    if ba[0] != 0 or np.any(sizes < 0) or n > codes_elems:
+        return False
+    # every segment sorted by itself, all at once (65536 segments x 16 ranks otherwise loop in Python)
+    seg = np.repeat(np.arange(nseg), sizes)
+    return np.array_equal(a[:n][np.lexsort((a[:n], seg))], b[:n][np.lexsort((b[:n], seg))])

@@ -5,7 +5,7 @@ GPU; what crosses the ranks is defined by the library's host-only functions,
 which phj_group.h itself calls and these tests drive through the C ABI:
   * phj_shard_range: rows of each rank (range shards, §8(e));
   * phj_exchange_layout: one rank's all-gathered block, build codes in final
-    partition order | zero padding | bounds[P + 1] (uint32);
+    partition order | padding (unspecified, never read) | bounds[P + 1] (uint32);
   * phj_count_contribution / phj_count_verdict: the {count, failed} words of
     the count all-reduce and the global count (or PHJ_ERR_STATE) they give.
 Each rank's packed block is built by tests/exchange_proto.py from the oracle's

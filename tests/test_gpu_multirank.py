@@ -179,16 +179,14 @@ def test_rccl_world_of_one_failed_rank(name, p):
         assert g.join(p).matches == expect
 
 
-@pytest.mark.parametrize("name,p", PARAMS[:2], ids=[a for a, _ in PARAMS[:2]])
-@pytest.mark.parametrize("world", [2, 3])
-def test_member_pack_matches_protocol(world, name, p):
-    """The library's own exchange blocks (the device pack of each member,
-    phj_debug_exchange_block) against the protocol's restatement
-    (tests/exchange_proto.py, the same pack tests/test_distributed.py runs over
-    gloo): layout, bounds and each segment's codes."""
+PACK_PARAMS = PARAMS[:2] + [   # the LDS join's clusters; the code tables' final partitions; keys, fully partitioned
+    ("radix-8+8-murmur3-stable", phj.radix_params((8, 8), hash=phj.HASH_MURMUR3, seed=SEED, stable=True)),
+    ("radix-mod5000-xxh3-stable", phj.radix_params(num_partitions=5000, hash=phj.HASH_XXH3, seed=2, stable=True)),
+    ("radix-8+8-murmur3-chained", phj.radix_params((8, 8), hash=phj.HASH_MURMUR3, seed=SEED, chained=True))]
+
+
+def _check_pack(world, name, p, R, S):
     import exchange_proto as X
-    R, S = O.generate_tables(300_007, 2_000_003, 1.05, 13, threads=4)
-    R[:, 0] = R[:, 0] * 7919 - 3   # spread keys: no structure in the codes
     nR = R.shape[0]
     with phj.Context(devices=[0] * world, flags=phj.CTX_LOCAL) as g:
         g.upload(phj.SIDE_BUILD, R)
@@ -202,3 +200,39 @@ def test_member_pack_matches_protocol(world, name, p):
             want = X.pack(R[lo:hi], p, nR, ce, be)
             got = g.debug_exchange_block(r, be)
             assert X.same_block(got, want, nseg, ce), (r, name)
+            if hi == lo:   # an empty shard: a valid empty segment, every bound 0
+                assert not np.any(got[ce:].view(np.uint32)[:nseg + 1]), (r, name)
+
+
+@pytest.mark.parametrize("name,p", PACK_PARAMS, ids=[a for a, _ in PACK_PARAMS])
+@pytest.mark.parametrize("world", [2, 3, 16])
+def test_member_pack_matches_protocol(world, name, p):
+    """The library's own exchange blocks (the device pack of each member,
+    phj_debug_exchange_block) against the protocol's restatement
+    (tests/exchange_proto.py, the same pack tests/test_distributed.py runs over
+    gloo): layout, bounds and each segment's codes. The
+    stable params take the code tables (their segments are the final
+    partitions, exchange_geometry's cluster == False); the chained ones ship
+    keys, as exchange_proto.pack restates."""
+    import exchange_proto as X
+    R, S = O.generate_tables(300_007, 2_000_003, 1.05, 13, threads=4)
+    R[:, 0] = R[:, 0] * 7919 - 3   # spread keys: no structure in the codes
+    cluster = phj.exchange_geometry(p, R.shape[0])[4]
+    assert cluster == (name in [a for a, _ in PARAMS[:2]])
+    assert X.ships_keys(p, R.shape[0]) == name.endswith("chained")
+    _check_pack(world, name, p, R, S)
+
+
+@pytest.mark.parametrize("name,p", PACK_PARAMS, ids=[a for a, _ in PACK_PARAMS])
+@pytest.mark.parametrize("world,shape", [(3, "5-rows"), (3, "2-rows"), (16, "5-rows"), (16, "edge-keys")])
+def test_member_pack_short_and_empty_shards(world, shape, name, p):
+    """Shards far shorter than the 64-element-padded block, and empty ones
+    (two rows over three ranks, five over sixteen: all their bounds 0); and
+    the keys whose codes are the tables' empty values and their bucket mates
+    (test_gpu_parity.edge_keys: code 0 among them, which the padding of
+    exchange_proto.pack also holds), 8-9 rows per rank at world 16."""
+    from test_gpu_parity import edge_keys
+    keys = edge_keys(p) if shape == "edge-keys" else np.array([7, -1, 0, 7, 2 ** 62], dtype=np.int64)[:int(shape[0])]
+    sizes = [hi - lo for lo, hi in (shard_range(len(keys), r, world) for r in range(world))]
+    assert (min(sizes) == 0) == (shape != "edge-keys" and (world, shape) != (3, "5-rows")) and max(sizes) < 64
+    _check_pack(world, name, p, O.as_relation(keys), O.as_relation(np.concatenate([keys, keys + 1])))
