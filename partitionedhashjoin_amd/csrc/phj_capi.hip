@@ -104,6 +104,12 @@ auto with_hash(int hk, F f) {
     return hk == kMurmur3 ? f(std::integral_constant<int, kMurmur3>{}) : f(std::integral_constant<int, kXXH3>{});
 }
 
+// ... and f(std::true_type / std::false_type) for a kernel template over a bool.
+template <class F>
+auto with_bool(bool b, F f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 int env_int(const char* name, int dflt) {
     const char* v = std::getenv(name);
     return (v && *v) ? std::atoi(v) : dflt;
@@ -2339,10 +2345,10 @@ int np_build(phj_ctx* c, const phj_join_params* p, bool slots32, NPHome& g, hipE
     return PHJ_OK;
 }
 
-// The NoPartitioning forms of the inner, row and aggregate joins (one probe of
-// the bucket table over the bound S, four tuples per thread): what they share
-// before their first probe kernel (np_setup) and at their end (np_times), as
-// FusedJoin does for the radix forms.
+// The NoPartitioning form of the row and aggregate joins (one probe of the
+// bucket table over the bound S, four tuples per thread): what comes before
+// the first probe kernel (np_setup) and at the end (np_times), as FusedJoin
+// has it for the radix form. The drivers see either one as a JoinForm.
 struct NPJoin {
     NPHome g{};
     hipEvent_t e0 = nullptr, e1 = nullptr;   // around the build
@@ -2792,10 +2798,10 @@ int mat_compact(phj_ctx* c, uint64_t nS, const longlong2* s_aos, const int64_t* 
     return timer_end(c);
 }
 
-// The radix forms of the materialised join and of the inner join (the fused
-// per-partition LDS join of both sides fully partitioned, SoA): what they
-// share before their first join kernel (fused_setup, fused_items) and at
-// their end (fused_times).
+// The radix forms of the materialised join and of the row and aggregate joins
+// (the fused per-partition LDS join of both sides fully partitioned, SoA):
+// what they share before their first join kernel (fused_setup, fused_items)
+// and at their end (fused_times).
 struct FusedJoin {
     Plan pl;
     uint32_t requested = 0;   // partitions asked for (pl may be refined)
@@ -2842,14 +2848,19 @@ int fused_setup(phj_ctx* c, const phj_join_params* p, const char* what, FusedJoi
     return PHJ_OK;
 }
 
-// Opens the first join kernel's timer (it reads the build keys and the probe
-// keys and writes a word per probe tuple) with the work items inside it.
-int fused_items(phj_ctx* c, const char* timer, const FusedJoin& j) {
-    PHJ_TRY(timer_begin(c, timer, c->side[PHJ_SIDE_BUILD].n * 8 + j.nS * 12));
+// The work items of the join kernels, written inside the first one's timer.
+int fused_work_items(phj_ctx* c, const FusedJoin& j) {
     hipLaunchKernelGGL(k_fused_items, dim3((j.fa.L.P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, j.fa.sbounds,
                        j.fa.L.P, static_cast<FusedItem*>(c->fitems.p));
     PHJ_LAUNCHED(c, "k_fused_items");
     return PHJ_OK;
+}
+
+// Opens the first join kernel's timer (it reads the build keys and the probe
+// keys and writes a word per probe tuple) with the work items inside it.
+int fused_items(phj_ctx* c, const char* timer, const FusedJoin& j) {
+    PHJ_TRY(timer_begin(c, timer, c->side[PHJ_SIDE_BUILD].n * 8 + j.nS * 12));
+    return fused_work_items(c, j);
 }
 
 // p1: the event behind the join's last kernel.
@@ -2888,13 +2899,8 @@ int join_radix_mark(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
 
 constexpr uint64_t kInnerRowLimit = 1ull << 32;   // rows are addressed with 32 bits (scan_u32)
 
-int inner_range_error(phj_ctx* c, uint64_t pairs) {
-    return set_err(c, PHJ_ERR_RANGE, "phj_join_inner: " + std::to_string(pairs) +
-                                         " pairs, rows are addressed with 32 bits (limit 2^32 - 1)");
-}
-
 // Pass 2 of the inner join: pairs[0, nS) (mat_mark) -> each probe tuple's
-// first row, in place. Launched inside the caller's "inner.emit" timer.
+// first row, in place. Launched inside the caller's emit timer.
 int inner_offsets(phj_ctx* c, uint64_t nS) {
     const uint32_t nblk = static_cast<uint32_t>((nS + kMatBlock - 1) / kMatBlock);
     auto* cnt = static_cast<uint32_t*>(c->mat_cnt.p);
@@ -2908,124 +2914,158 @@ int inner_offsets(phj_ctx* c, uint64_t nS) {
     return PHJ_OK;
 }
 
-// Bytes the two passes must move, beyond partitioning / the table build
-// (DESIGN.md §Inner join): the count pass reads the probe keys and the build
-// keys and writes pairs[]; the offsets read pairs[] twice and write it once;
-// the emit pass reads the build keys, the probe tuples and pairs[] again and,
-// per row, gathers a build payload and writes 24 B.
+// Bytes the count pass must move, beyond partitioning / the table build
+// (DESIGN.md §Inner join): it reads the probe keys and the build keys and
+// writes pairs[]. (The emit pass: rows_emit_bytes.)
 uint64_t inner_count_bytes(uint64_t nR, uint64_t nS) { return nR * 8 + nS * (8 + 4); }
-uint64_t inner_emit_bytes(uint64_t nS, uint64_t rows) {   // (without the build side)
-    return nS * 12 + nS * (16 + 4) + rows * (8 + 24);
+
+// The two index columns of n rows in the row buffer (phj_ctx::idx_n).
+IndexSink index_sink(phj_ctx* c, uint64_t n) {
+    int64_t* base = static_cast<int64_t*>(c->mat_rows.p);
+    return IndexSink{base, base + n};
 }
 
-// Passes 2 and 3 after a count of r->matches pairs over nS probe tuples:
-// the row limit, the workspace, then offsets and launch(rows) (the join again,
-// emitting) in the "inner.emit" timer; *end: the event behind it. build_bytes:
-// what the emit pass reads of the build side (its keys, or the bucket table).
+// Where the emitting kernels store: the row buffer as 24-B rows, or as the two
+// index columns (phj_join_indices). f(sink) with the one in use, so that a
+// kernel template over the sink is named once per launch site.
+struct RowSinks {
+    JoinedRow* rows;
+    IndexSink index;
+};
 template <class F>
-int inner_emit(phj_ctx* c, phj_join_result* r, uint64_t nS, uint64_t build_bytes, hipEvent_t* end, F launch) {
-    const uint64_t m = r->matches;
-    // nothing is written and the row buffer is not grown above the limit
-    if (m >= kInnerRowLimit) return inner_range_error(c, m);
-    const uint32_t nblk = static_cast<uint32_t>((nS + kMatBlock - 1) / kMatBlock);
-    PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
-    PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, m) * sizeof(JoinedRow)));
-    const uint64_t bytes = inner_emit_bytes(nS, m) + build_bytes;
-    PHJ_TRY(timer_begin(c, "inner.emit", bytes));
-    PHJ_TRY(inner_offsets(c, nS));
-    PHJ_TRY(launch(static_cast<JoinedRow*>(c->mat_rows.p)));
-    PHJ_TRY(timer_end(c));
-    PHJ_TRY(mark(c, end));
-    PHJ_HIP(c, hipStreamSynchronize(c->ks));
-    r->algorithmic_bytes += bytes;
+void with_sink(bool index, const RowSinks& s, F f) {
+    if (index) f(s.index);
+    else f(s.rows);
+}
+
+// ---- the join form: what the row and aggregate joins run on ----
+
+// A join set up in its NoPartitioning form (np_setup: the bucket table built,
+// S probed where it is bound) or its radix form (fused_setup: both sides fully
+// partitioned, SoA, for the per-partition LDS join), as the passes behind it
+// see either: the probe side in storage order (pairs[] has one word per
+// tuple), the build storage that hit flags and accumulators index, the bytes
+// and the report of what ran so far.
+struct JoinForm {
+    NPJoin np;      // NoPartitioning (tab != nullptr)
+    FusedJoin fu;   // radix
+    int hk = 0;
+    uint64_t seed = 0;
+    uint64_t nS = 0;
+    const longlong2* s_aos = nullptr;             // NoPartitioning: AoS tuples
+    const int64_t *sk = nullptr, *sp = nullptr;   // radix: the partitioned columns
+    uint64_t nF = 0;                              // elements of the build storage
+    const NPBucket* tab = nullptr;                // NoPartitioning: the table (keys), rp = np_pays
+    const int64_t *rk = nullptr, *rp = nullptr;
+    // phj_join_indices: the payloads the join carries are row numbers (sp, rp;
+    // NoPartitioning: s_aos and sk are null and a probe tuple's number is its
+    // position) and the emit pass stores into the two index columns.
+    // NoPartitioning reads S for its keys alone (k_np_inner KEYS): keys = 1 its
+    // key column itself, 2 its tuples' ids, 0 whole tuples.
+    bool index = false;
+    int keys = 0;
+    const longlong2* s_probe = nullptr;
+    // what a pass reads of the build side (its keys, or the bucket table), the
+    // table alone, the count pass, and everything before the first join kernel
+    uint64_t build_bytes = 0, table_bytes = 0, count_bytes = 0, front_bytes = 0;
+    uint32_t num_partitions = 0;
+};
+
+// The limits, the workspace that is sized ahead of the build, then the form.
+// what: the radix form's name in its precondition ("<what> needs ...").
+// pairs: the join counts into pairs[] and the count words {pairs, probe_only,
+// build_only} (the first one cleared here); the aggregates have words of their own.
+int form_setup(phj_ctx* c, const phj_join_params* p, const char* what, bool pairs, bool index, JoinForm& J) {
+    const SideState& R = c->side[PHJ_SIDE_BUILD];
+    const SideState& S = c->side[PHJ_SIDE_PROBE];
+    const PaySrc pay = index ? PaySrc::RowNumber : PaySrc::Bound;
+    J.index = index;
+    if (p->algo == PHJ_ALGO_NO_PARTITIONING) {
+        PHJ_TRY(np_limits(c, p));
+        if (pairs) {
+            PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));   // a word per probe tuple, sized before the build
+            PHJ_TRY(ensure(c, c->count, 32));
+        }
+        PHJ_TRY(np_setup(c, p, true, pay, J.np));
+        if (pairs) PHJ_HIP(c, hipMemsetAsync(J.np.cnt, 0, 8, c->ks));
+        J.hk = p->hash;
+        J.seed = p->hash_seed;
+        J.keys = !index ? 0 : S.columns ? 1 : 2;
+        J.s_probe = J.keys == 1 ? reinterpret_cast<const longlong2*>(S.ckeys) : J.np.S_rel;
+        J.nS = S.n;
+        J.s_aos = index ? nullptr : J.np.S_rel;
+        J.nF = static_cast<uint64_t>(J.np.g.nb) * kNPSlots;
+        J.tab = J.np.tab;
+        J.rp = J.np.pays;
+        J.table_bytes = J.build_bytes = J.np.table_bytes;
+        J.count_bytes = inner_count_bytes(0, S.n) + J.table_bytes;
+        J.front_bytes = R.n * 32 + J.table_bytes;
+        return PHJ_OK;
+    }
+    if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
+    if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
+    PHJ_TRY(fused_setup(c, p, what, J.fu, pay));   // (pairs[] and the count words are its own workspace)
+    J.hk = J.fu.pl.hk;
+    J.nS = J.fu.nS;
+    J.sk = S.view.keys;
+    J.sp = S.view.payloads;
+    J.nF = R.view.n;
+    J.rk = R.view.keys;
+    J.rp = R.view.payloads;
+    J.build_bytes = R.n * 8;
+    J.count_bytes = inner_count_bytes(R.n, J.nS);
+    // (a key column's pass 1 reads 8 B per tuple less in each of its reads)
+    J.front_bytes = partition_bytes(J.fu.pl, R.n) + partition_bytes(J.fu.pl, S.n) -
+                    (index && R.columns ? R.n * 16 : 0) - (index && S.columns ? S.n * 16 : 0);
+    J.num_partitions = J.fu.requested;
     return PHJ_OK;
 }
 
-int join_nopart_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit) {
-    SideState& R = c->side[PHJ_SIDE_BUILD];
-    SideState& S = c->side[PHJ_SIDE_PROBE];
-    PHJ_TRY(np_limits(c, p));
-    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));   // pairs[]: a word per probe tuple, sized before the build
-    NPJoin j;
-    PHJ_TRY(np_setup(c, p, true, PaySrc::Bound, j));
-    PHJ_HIP(c, hipMemsetAsync(j.cnt, 0, 8, c->ks));
+// end: the event behind the join's last kernel.
+int form_times(phj_ctx* c, const JoinForm& J, hipEvent_t end, phj_join_result* r) {
+    return J.tab ? np_times(c, J.np.e0, J.np.e1, end, r) : fused_times(c, J.fu, end, r);
+}
+
+// k_np_inner / k_inner_fused over the form: the count pass (the radix form's
+// work items before it), the count pass that also marks the build tuples it
+// hits (the flags, c->row_hit, travel in its unused row pointer, phj_inner.h),
+// and the emit pass of nrows rows into the sink in use.
+enum class InnerPass { Count, CountMark, Emit };
+
+int inner_pass(phj_ctx* c, const JoinForm& J, InnerPass pass, const RowSinks& out = {}, uint32_t nrows = 0) {
     auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
-    const uint64_t table_bytes = j.table_bytes;
-    hipEvent_t e2;
-    auto launch = [&](auto e, JoinedRow* rows, uint32_t nrows) -> int {
-        with_hash(p->hash, [&](auto h) {
-            hipLaunchKernelGGL((k_np_inner<decltype(h)::value, decltype(e)::value>), dim3(j.grid), dim3(kBlock), 0, c->ks,
-                               j.S_rel, S.n, j.tab, j.pays, j.g, p->hash_seed, pairs, j.cnt, rows, nrows);
+    JoinedRow* const flags = pass == InnerPass::CountMark ? static_cast<JoinedRow*>(c->row_hit.p) : nullptr;
+    if (J.tab) {
+        auto np = [&](auto h, auto keys, auto sink) {
+            constexpr int HK = decltype(h)::value, KEYS = decltype(keys)::value;
+            auto go = [&](auto kernel, auto to) {
+                hipLaunchKernelGGL(kernel, dim3(J.np.grid), dim3(kBlock), 0, c->ks, J.s_probe, J.nS, J.tab, J.rp, J.np.g,
+                                   J.seed, pairs, J.np.cnt, to, nrows);
+            };
+            if (pass == InnerPass::Emit) go(k_np_inner<HK, true, false, decltype(sink), KEYS>, sink);
+            else if (pass == InnerPass::CountMark) go(k_np_inner<HK, false, true, JoinedRow*, KEYS>, flags);
+            else go(k_np_inner<HK, false, false, JoinedRow*, KEYS>, flags);
+        };
+        with_hash(J.hk, [&](auto h) {   // (the index columns go with KEYS 1 or 2 and with nothing else)
+            if (!J.index) np(h, std::integral_constant<int, 0>{}, out.rows);
+            else if (J.keys == 1) np(h, std::integral_constant<int, 1>{}, out.index);
+            else np(h, std::integral_constant<int, 2>{}, out.index);
         });
         PHJ_LAUNCHED(c, "k_np_inner");
         return PHJ_OK;
-    };
-    PHJ_TRY(timer_begin(c, "inner.count", inner_count_bytes(0, S.n) + table_bytes));
-    PHJ_TRY(launch(std::false_type{}, nullptr, 0u));
-    PHJ_TRY(timer_end(c));
-    PHJ_TRY(mark(c, &e2));
-    uint64_t m = 0;
-    PHJ_TRY(get_count(c, &m));
-    r->matches = m;
-    r->algorithmic_bytes = R.n * 32 + table_bytes + inner_count_bytes(0, S.n) + table_bytes;
-    if (emit)
-        PHJ_TRY(inner_emit(c, r, S.n, table_bytes, &e2, [&](JoinedRow* rows) {
-            return launch(std::true_type{}, rows, static_cast<uint32_t>(m));
-        }));
-    return np_times(c, j.e0, j.e1, e2, r);
-}
-
-// The radix form: both sides fully partitioned (SoA), then the per-partition
-// LDS join twice (join_radix_mark's precondition: the fused LDS join).
-int join_radix_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit) {
-    const SideState& R = c->side[PHJ_SIDE_BUILD];
-    const SideState& S = c->side[PHJ_SIDE_PROBE];
-    if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
-    if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
-    FusedJoin j;
-    PHJ_TRY(fused_setup(c, p, "radix inner join", j));
-    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
-    auto launch = [&](auto e, JoinedRow* rows, uint32_t nrows) -> int {
-        with_hash(j.pl.hk, [&](auto h) {
-            hipLaunchKernelGGL((k_inner_fused<decltype(h)::value, decltype(e)::value>), dim3(j.grid), dim3(kBlock), 0,
-                               c->ks, j.fa, pairs, S.view.payloads, rows, nrows);
-        });
-        PHJ_LAUNCHED(c, "k_inner_fused");
-        return PHJ_OK;
-    };
-    PHJ_TRY(fused_items(c, "inner.count", j));
-    PHJ_TRY(launch(std::false_type{}, nullptr, 0u));
-    PHJ_TRY(timer_end(c));
-    hipEvent_t p1;
-    PHJ_TRY(mark(c, &p1));
-    uint64_t m = 0;
-    PHJ_TRY(get_count(c, &m));
-    r->matches = m;
-    r->num_partitions = j.requested;
-    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n) + inner_count_bytes(R.n, j.nS);
-    if (emit)
-        PHJ_TRY(inner_emit(c, r, j.nS, R.n * 8, &p1, [&](JoinedRow* rows) {
-            return launch(std::true_type{}, rows, static_cast<uint32_t>(m));
-        }));
-    return fused_times(c, j, p1, r);
-}
-
-// phj_join_inner_count (emit = false) / phj_join_inner.
-int join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r, bool emit, const char* what) {
-    if (!c || !r) return PHJ_ERR_INVALID;
-    if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
-    if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
-    PHJ_TRY(begin_call(c));
-    std::memset(r, 0, sizeof(*r));
-    if (emit) c->mat_n = c->idx_n = 0;   // (the index columns of phj_join_indices lie in the same buffer)
-    if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
-        return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
-    PHJ_TRY(need_tuples_both(c, emit, what));   // (sides bound as columns)
-    // an empty side joins to nothing (no table to build, no pass to run)
-    if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0) return PHJ_OK;
-    if (p->algo == PHJ_ALGO_NO_PARTITIONING) PHJ_TRY(join_nopart_inner(c, p, r, emit));
-    else PHJ_TRY(join_radix_inner(c, p, r, emit));
-    if (emit) c->mat_n = r->matches;
+    }
+    if (pass != InnerPass::Emit) PHJ_TRY(fused_work_items(c, J.fu));
+    with_hash(J.hk, [&](auto h) {
+        constexpr int HK = decltype(h)::value;
+        auto go = [&](auto kernel, auto to) {
+            hipLaunchKernelGGL(kernel, dim3(J.fu.grid), dim3(kBlock), 0, c->ks, J.fu.fa, pairs, J.sp, to, nrows);
+        };
+        if (pass == InnerPass::Emit)
+            with_sink(J.index, out, [&](auto sink) { go(k_inner_fused<HK, true, false, decltype(sink)>, sink); });
+        else if (pass == InnerPass::CountMark) go(k_inner_fused<HK, false, true>, flags);
+        else go(k_inner_fused<HK, false>, flags);
+    });
+    PHJ_LAUNCHED(c, "k_inner_fused");
     return PHJ_OK;
 }
 
@@ -3040,29 +3080,39 @@ uint64_t agg_join_bytes(uint64_t nR, uint64_t nS) { return nR * 16 + nS * 16; }
 uint64_t agg_clear_bytes(uint64_t nF) { return nF * 16; }
 uint64_t agg_compact_bytes(uint64_t nF, uint64_t rows) { return nF * 16 + rows * 32; }
 
-// What the two algorithms hand to agg_passes: the build storage the
-// accumulators index and their join kernel.
-struct AggJob {
-    uint64_t nF = 0;                              // elements of the build storage
-    const NPBucket* tab = nullptr;                // NoPartitioning: the table (keys), rp = np_pays
-    const int64_t *rk = nullptr, *rp = nullptr;
-    uint64_t join_bytes = 0;
-    std::function<int(unsigned long long*, unsigned long long*)> join;   // (result words, accumulator planes)
-};
+// k_np_agg / k_agg_fused over the form (the radix form's work items before
+// it): the totals into res and, with acc, the accumulator planes.
+int agg_pass(phj_ctx* c, const JoinForm& J, unsigned long long* res, unsigned long long* acc) {
+    if (!J.tab) PHJ_TRY(fused_work_items(c, J.fu));
+    with_hash(J.hk, [&](auto h) {
+        with_bool(acc != nullptr, [&](auto groups) {
+            constexpr int HK = decltype(h)::value;
+            constexpr bool GROUPS = decltype(groups)::value;
+            if (J.tab)
+                hipLaunchKernelGGL((k_np_agg<HK, GROUPS>), dim3(J.np.grid), dim3(kBlock), 0, c->ks, J.np.S_rel, J.nS, J.tab,
+                                   J.rp, J.np.g, J.seed, res, acc, J.nF);
+            else
+                hipLaunchKernelGGL((k_agg_fused<HK, GROUPS>), dim3(J.fu.grid), dim3(kBlock), 0, c->ks, J.fu.fa, J.sp, res, acc,
+                                   J.nF);
+        });
+    });
+    PHJ_LAUNCHED(c, (J.tab ? "k_np_agg" : "k_agg_fused"));
+    return PHJ_OK;
+}
 
 // Everything behind the partitioning / table build: the result words and
 // (groups) the planes cleared, the accumulating pass, the compaction. One
 // stream, one synchronisation at the end; *end: the event behind the last kernel.
-int agg_passes(phj_ctx* c, uint32_t flags, const AggJob& J, phj_join_result* r, phj_join_totals* t, hipEvent_t* end) {
+int agg_passes(phj_ctx* c, uint32_t flags, const JoinForm& J, phj_join_result* r, phj_join_totals* t, hipEvent_t* end) {
     const bool groups = flags & PHJ_AGG_GROUPS, matched = flags & PHJ_AGG_MATCHED_ONLY;
-    const bool np = J.tab != nullptr;
+    const uint64_t nR = c->side[PHJ_SIDE_BUILD].n;
     const uint32_t fblk = static_cast<uint32_t>((J.nF + kMatBlock - 1) / kMatBlock);
     PHJ_TRY(ensure(c, c->agg_res, 64));
     if (groups) {
         PHJ_TRY(ensure(c, c->agg_acc, J.nF * 16));
         PHJ_TRY(ensure(c, c->agg_cnt, (static_cast<size_t>(fblk) + 1) * 4));
         // (every build tuple may get a row; sized before the launch so that nothing is allocated between the passes)
-        PHJ_TRY(ensure(c, c->agg_rows, std::max<uint64_t>(1, c->side[PHJ_SIDE_BUILD].n) * sizeof(GroupRow)));
+        PHJ_TRY(ensure(c, c->agg_rows, std::max<uint64_t>(1, nR) * sizeof(GroupRow)));
     }
     auto* res = static_cast<unsigned long long*>(c->agg_res.p);   // {5 totals, group rows}
     auto* acc = static_cast<unsigned long long*>(c->agg_acc.p);
@@ -3076,23 +3126,27 @@ int agg_passes(phj_ctx* c, uint32_t flags, const AggJob& J, phj_join_result* r, 
         c->since_ev++;
         PHJ_TRY(timer_end(c));
     }
-    const uint64_t jbytes = J.join_bytes + (groups ? J.nF * 16 : 0);
+    const uint64_t jbytes = (J.tab ? agg_join_bytes(0, J.nS) + J.table_bytes + nR * 8 : agg_join_bytes(nR, J.nS)) +
+                            (groups ? J.nF * 16 : 0);
     r->algorithmic_bytes += jbytes;
     PHJ_TRY(timer_begin(c, "agg.join", jbytes));
-    PHJ_TRY(J.join(res, groups ? acc : nullptr));
+    PHJ_TRY(agg_pass(c, J, res, groups ? acc : nullptr));
     PHJ_TRY(timer_end(c));
-    const uint64_t nrows_max = c->side[PHJ_SIDE_BUILD].n;
     if (groups) {
         // (the rows written are only known afterwards: the timer carries the planes, the result adds the rows)
         PHJ_TRY(timer_begin(c, "agg.groups", agg_compact_bytes(J.nF, 0)));
         PHJ_HIP(c, hipMemsetAsync(bcnt, 0, (static_cast<size_t>(fblk) + 1) * 4, c->ks));
         auto* rows = static_cast<GroupRow*>(c->agg_rows.p);
-        if (np) hipLaunchKernelGGL(k_agg_group_count<true>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, bcnt, res + kAggTotals);
-        else hipLaunchKernelGGL(k_agg_group_count<false>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, bcnt, res + kAggTotals);
+        with_bool(J.tab != nullptr, [&](auto np) {
+            hipLaunchKernelGGL(k_agg_group_count<decltype(np)::value>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF,
+                               matched, bcnt, res + kAggTotals);
+        });
         PHJ_LAUNCHED(c, "k_agg_group_count");
         PHJ_TRY(scan_u32(c, bcnt, fblk + 1, 1, fblk + 1));
-        if (np) hipLaunchKernelGGL(k_agg_group_write<true>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, J.rk, J.rp, bcnt, rows, nrows_max);
-        else hipLaunchKernelGGL(k_agg_group_write<false>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF, matched, J.rk, J.rp, bcnt, rows, nrows_max);
+        with_bool(J.tab != nullptr, [&](auto np) {
+            hipLaunchKernelGGL(k_agg_group_write<decltype(np)::value>, dim3(fblk), dim3(kBlock), 0, c->ks, acc, J.tab, J.nF,
+                               matched, J.rk, J.rp, bcnt, rows, nR);
+        });
         PHJ_LAUNCHED(c, "k_agg_group_write");
         PHJ_TRY(timer_end(c));
     }
@@ -3108,77 +3162,11 @@ int agg_passes(phj_ctx* c, uint32_t flags, const AggJob& J, phj_join_result* r, 
     t->sum_ab = static_cast<int64_t>(h[4]);
     r->matches = t->pairs;
     if (groups) {
-        if (h[kAggTotals] > nrows_max) return set_err(c, PHJ_ERR_STATE, "phj_join_aggregate: more group rows than build tuples");
+        if (h[kAggTotals] > nR) return set_err(c, PHJ_ERR_STATE, "phj_join_aggregate: more group rows than build tuples");
         c->agg_n = h[kAggTotals];
         r->algorithmic_bytes += agg_compact_bytes(J.nF, c->agg_n);
     }
     return PHJ_OK;
-}
-
-int join_nopart_agg(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_join_result* r, phj_join_totals* t) {
-    SideState& R = c->side[PHJ_SIDE_BUILD];
-    SideState& S = c->side[PHJ_SIDE_PROBE];
-    NPJoin j;
-    PHJ_TRY(np_limits(c, p));
-    PHJ_TRY(np_setup(c, p, true, PaySrc::Bound, j));   // (no count word to clear: the totals land in agg_res)
-    hipEvent_t e2;
-    AggJob J;
-    J.nF = static_cast<uint64_t>(j.g.nb) * kNPSlots;
-    J.tab = j.tab;
-    J.rp = j.pays;
-    J.join_bytes = agg_join_bytes(0, S.n) + j.table_bytes + R.n * 8;
-    J.join = [&](unsigned long long* res, unsigned long long* acc) -> int {
-        with_hash(p->hash, [&](auto h) {
-            constexpr int HK = decltype(h)::value;
-            if (acc)
-                hipLaunchKernelGGL((k_np_agg<HK, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.S_rel, S.n, j.tab, j.pays, j.g,
-                                   p->hash_seed, res, acc, J.nF);
-            else
-                hipLaunchKernelGGL((k_np_agg<HK, false>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.S_rel, S.n, j.tab, j.pays, j.g,
-                                   p->hash_seed, res, acc, J.nF);
-        });
-        PHJ_LAUNCHED(c, "k_np_agg");
-        return PHJ_OK;
-    };
-    r->algorithmic_bytes = R.n * 32 + j.table_bytes;
-    PHJ_TRY(agg_passes(c, flags, J, r, t, &e2));
-    return np_times(c, j.e0, j.e1, e2, r);
-}
-
-// The radix form: join_radix_inner's precondition and partitioning.
-int join_radix_agg(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_join_result* r, phj_join_totals* t) {
-    const SideState& R = c->side[PHJ_SIDE_BUILD];
-    const SideState& S = c->side[PHJ_SIDE_PROBE];
-    if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
-    if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
-    FusedJoin j;
-    PHJ_TRY(fused_setup(c, p, "radix aggregate join", j));
-    AggJob J;
-    J.nF = R.view.n;
-    J.rk = R.view.keys;
-    J.rp = R.view.payloads;
-    J.join_bytes = agg_join_bytes(R.n, j.nS);
-    J.join = [&](unsigned long long* res, unsigned long long* acc) -> int {
-        hipLaunchKernelGGL(k_fused_items, dim3((j.fa.L.P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, j.fa.sbounds,
-                           j.fa.L.P, static_cast<FusedItem*>(c->fitems.p));
-        PHJ_LAUNCHED(c, "k_fused_items");
-        with_hash(j.pl.hk, [&](auto h) {
-            constexpr int HK = decltype(h)::value;
-            if (acc)
-                hipLaunchKernelGGL((k_agg_fused<HK, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, S.view.payloads,
-                                   res, acc, J.nF);
-            else
-                hipLaunchKernelGGL((k_agg_fused<HK, false>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, S.view.payloads,
-                                   res, acc, J.nF);
-        });
-        PHJ_LAUNCHED(c, "k_agg_fused");
-        return PHJ_OK;
-    };
-    r->num_partitions = j.requested;
-    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n);
-    hipEvent_t p1;
-    PHJ_TRY(agg_passes(c, flags, J, r, t, &p1));
-    return fused_times(c, j, p1, r);
 }
 
 // An empty probe side with groups of every build tuple: rows copied from the
@@ -3224,75 +3212,66 @@ int join_aggregate(phj_ctx* c, const phj_join_params* p, uint32_t flags, phj_joi
         if (nR > 0 && flags == PHJ_AGG_GROUPS) PHJ_TRY(agg_empty_probe(c, r));
         return PHJ_OK;
     }
-    if (p->algo == PHJ_ALGO_NO_PARTITIONING) return join_nopart_agg(c, p, flags, r, t);
-    return join_radix_agg(c, p, flags, r, t);
+    JoinForm J;
+    PHJ_TRY(form_setup(c, p, "radix aggregate join", false, false, J));   // (the totals land in agg_res)
+    r->num_partitions = J.num_partitions;
+    r->algorithmic_bytes = J.front_bytes;
+    hipEvent_t end;
+    PHJ_TRY(agg_passes(c, flags, J, r, t, &end));
+    return form_times(c, J, end, r);
 }
 
 // ---- rows by class (phj_outer.h): pairs, probe-only, build-only ----
 
-// What the passes of phj_join_rows must move beyond the inner join's
-// (DESIGN.md §Outer and anti joins). F = bytes of hit flags, one per element
-// of the build storage. Count: the inner count pass; with build-only rows the
-// flags cleared and (at most) every one stored; with probe-only rows pairs[]
-// read and written and the bitmap written. Emit: the offsets (pairs[] read
-// twice, written once); with pair rows the inner emit pass; the bitmap read
-// and, per null row, its offset, its probe tuple and 24 B written. Build-only:
-// the flags read twice (count, write; NoPartitioning: with the table beside
-// them) and, per row, a build tuple read and 24 B written.
+// What the passes of phj_join_rows must move beyond partitioning / the table
+// build (DESIGN.md §Inner join, §Outer and anti joins). F = bytes of hit
+// flags, one per element of the build storage. Count: the inner count pass;
+// with build-only rows the flags cleared and (at most) every one stored; with
+// probe-only rows pairs[] read and written and the bitmap written. Emit: the
+// offsets (pairs[] read twice, written once); with the pair pass the build
+// keys (or the table), the probe tuples and pairs[] read again and, per row, a
+// build payload gathered and the row written; the bitmap read and, per null
+// row, its offset, its probe tuple and the row written. Build-only: the flags
+// read twice (count, write; NoPartitioning: with the table beside them) and,
+// per row, a build tuple read and the row written.
 uint64_t rows_count_bytes(uint64_t inner_count, uint64_t F, uint64_t nS, uint32_t classes) {
     return inner_count + ((classes & PHJ_ROWS_BUILD_ONLY) ? 2 * F : 0) +
            ((classes & PHJ_ROWS_PROBE_ONLY) ? nS * 8 + nS / 8 : 0);
 }
 // row: bytes written per row, 24 (phj_joined) or 16 (the two index columns).
-uint64_t rows_emit_bytes(uint64_t nS, uint64_t pair_rows, uint64_t probe_only, uint64_t build_bytes, uint64_t row = 24) {
-    return nS * 12 + (pair_rows ? build_bytes + nS * (16 + 4) + pair_rows * (8 + row) : 0) +
+uint64_t rows_emit_bytes(uint64_t nS, bool pair_pass, uint64_t pair_rows, uint64_t probe_only, uint64_t build_bytes,
+                         uint64_t row) {
+    return nS * 12 + (pair_pass ? build_bytes + nS * (16 + 4) + pair_rows * (8 + row) : 0) +
            (probe_only ? nS / 8 + probe_only * (4 + 16 + row) : 0);
 }
 uint64_t rows_build_only_bytes(uint64_t F, uint64_t table_bytes, uint64_t build_only, bool write, uint64_t row = 24) {
     return F + table_bytes + (write ? build_only * (16 + row) : 0);
 }
 
-int rows_range_error(phj_ctx* c, uint64_t rows, bool index = false) {
-    return set_err(c, PHJ_ERR_RANGE, std::string(index ? "phj_join_indices: " : "phj_join_rows: ") + std::to_string(rows) +
-                                         " rows, rows are addressed with 32 bits (limit 2^32 - 1)");
-}
-
-// What the two algorithms hand to rows_passes: the probe side in storage
-// order (pairs[] has one word per tuple), the build storage the hit flags
-// index, and their join kernel as count pass (bmark: also marking into
-// c->row_hit) and as emit pass.
-struct RowsJob {
-    uint64_t nS = 0;
-    const longlong2* s_aos = nullptr;             // NoPartitioning: AoS tuples
-    const int64_t *sk = nullptr, *sp = nullptr;   // radix: the partitioned columns
-    uint64_t nF = 0;                              // elements of the build storage
-    const NPBucket* tab = nullptr;                // NoPartitioning: the table (keys), rp = np_pays
-    const int64_t *rk = nullptr, *rp = nullptr;
-    uint64_t count_bytes = 0, build_bytes = 0, table_bytes = 0;
-    std::function<int(bool)> count;
-    std::function<int(JoinedRow*, uint32_t)> emit;
-    // phj_join_indices: the payloads the join carries are row numbers (sp, rp;
-    // NoPartitioning: s_aos and sk are null and a probe tuple's number is its
-    // position) and the emit pass stores into the two index columns
-    bool index = false;
-    std::function<int(IndexSink, uint32_t)> emit_index;
+// Where the row driver's two callers differ: phj_join_rows / phj_join_indices
+// and phj_join_inner, which is their class PHJ_ROWS_PAIRS under older names.
+struct RowsLabels {
+    const char *count, *emit;   // the timers
+    const char* radix;          // the radix form in its precondition message
+    const char* unit;           // what the 2^32 message counts
+    bool emit_always;           // the pair pass runs, and is accounted, with no pair to write
 };
+constexpr RowsLabels kRowsLabels{"rows.count", "rows.emit", "radix row join", "rows", false};
+constexpr RowsLabels kInnerLabels{"inner.count", "inner.emit", "radix inner join", "pairs", true};
 
-// The two index columns of n rows in the row buffer (phj_ctx::idx_n).
-IndexSink index_sink(phj_ctx* c, uint64_t n) {
-    int64_t* base = static_cast<int64_t*>(c->mat_rows.p);
-    return IndexSink{base, base + n};
+int rows_range_error(phj_ctx* c, const char* what, uint64_t rows, const char* unit = kRowsLabels.unit) {
+    return set_err(c, PHJ_ERR_RANGE, std::string(what) + ": " + std::to_string(rows) + " " + unit +
+                                         ", rows are addressed with 32 bits (limit 2^32 - 1)");
 }
 
 // Everything behind the partitioning / table build: the count pass (with hit
 // marking) and the reductions, the counts read back, then (emit) the 2^32
 // rule, offsets, pair rows, null rows and the unhit build tuples. One stream,
 // one synchronisation at the end; *end: the event behind the last kernel.
-int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, const RowsJob& J, phj_join_result* r,
-                phj_row_counts* n, hipEvent_t* end) {
+int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, const char* what, const RowsLabels& L,
+                const JoinForm& J, phj_join_result* r, phj_row_counts* n, hipEvent_t* end) {
     const bool want_p = classes & PHJ_ROWS_PAIRS, want_s = classes & PHJ_ROWS_PROBE_ONLY,
                want_b = classes & PHJ_ROWS_BUILD_ONLY;
-    const bool np = J.tab != nullptr;
     const uint32_t nblk = static_cast<uint32_t>((J.nS + kMatBlock - 1) / kMatBlock);
     const uint32_t fblk = static_cast<uint32_t>((J.nF + kMatBlock - 1) / kMatBlock);
     if (want_s) PHJ_TRY(ensure(c, c->row_only, (J.nS + 63) / 64 * 8));
@@ -3308,12 +3287,13 @@ int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, c
     PHJ_HIP(c, hipMemsetAsync(cnt + 1, 0, 16, c->ks));
     uint64_t bytes = rows_count_bytes(J.count_bytes, J.nF, J.nS, classes);
     r->algorithmic_bytes += bytes;
-    PHJ_TRY(timer_begin(c, "rows.count", bytes));
+    PHJ_TRY(timer_begin(c, L.count, bytes));
     if (want_b) PHJ_HIP(c, hipMemsetAsync(hit, 0, J.nF, c->ks));   // on every call: never the allocation's contents
-    PHJ_TRY(J.count(want_b));
+    PHJ_TRY(inner_pass(c, J, want_b ? InnerPass::CountMark : InnerPass::Count));
     if (want_s) {
-        if (want_p) hipLaunchKernelGGL(k_rows_map<true>, dim3(nblk), dim3(kBlock), 0, c->ks, pairs, J.nS, only, cnt + 1);
-        else hipLaunchKernelGGL(k_rows_map<false>, dim3(nblk), dim3(kBlock), 0, c->ks, pairs, J.nS, only, cnt + 1);
+        with_bool(want_p, [&](auto wp) {
+            hipLaunchKernelGGL(k_rows_map<decltype(wp)::value>, dim3(nblk), dim3(kBlock), 0, c->ks, pairs, J.nS, only, cnt + 1);
+        });
         PHJ_LAUNCHED(c, "k_rows_map");
     }
     PHJ_TRY(timer_end(c));
@@ -3322,8 +3302,10 @@ int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, c
         r->algorithmic_bytes += bytes;
         PHJ_TRY(timer_begin(c, "rows.build_only", bytes));
         PHJ_HIP(c, hipMemsetAsync(bcnt, 0, (static_cast<size_t>(fblk) + 1) * 4, c->ks));
-        if (np) hipLaunchKernelGGL(k_build_only_count<true>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, bcnt, cnt + 2);
-        else hipLaunchKernelGGL(k_build_only_count<false>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, bcnt, cnt + 2);
+        with_bool(J.tab != nullptr, [&](auto np) {
+            hipLaunchKernelGGL(k_build_only_count<decltype(np)::value>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF,
+                               bcnt, cnt + 2);
+        });
         PHJ_LAUNCHED(c, "k_build_only_count");
         PHJ_TRY(timer_end(c));
     }
@@ -3342,26 +3324,24 @@ int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, c
     if (!emit) return PHJ_OK;
     // nothing is written and the row buffer is not grown above the limit
     // (below it no block sum of the offsets can have wrapped either)
-    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows, J.index);
+    if (n->rows >= kInnerRowLimit) return rows_range_error(c, what, n->rows, L.unit);
     const uint64_t row_bytes = J.index ? 2 * sizeof(int64_t) : sizeof(JoinedRow);
     PHJ_TRY(ensure(c, c->mat_cnt, (static_cast<size_t>(nblk) + 1) * 4));
     PHJ_TRY(ensure(c, c->mat_rows, std::max<uint64_t>(1, n->rows) * row_bytes));
-    auto* rows = static_cast<JoinedRow*>(c->mat_rows.p);
-    const IndexSink isink = index_sink(c, n->rows);
-    if (probe_rows > 0) {
-        bytes = rows_emit_bytes(J.nS, pair_rows, n->probe_only, J.build_bytes, row_bytes);
+    const RowSinks out{static_cast<JoinedRow*>(c->mat_rows.p), index_sink(c, n->rows)};
+    const bool pair_pass = pair_rows > 0 || L.emit_always;
+    if (probe_rows > 0 || pair_pass) {
+        bytes = rows_emit_bytes(J.nS, pair_pass, pair_rows, n->probe_only, J.build_bytes, row_bytes);
         r->algorithmic_bytes += bytes;
-        PHJ_TRY(timer_begin(c, "rows.emit", bytes));
+        PHJ_TRY(timer_begin(c, L.emit, bytes));
         PHJ_TRY(inner_offsets(c, J.nS));
-        if (pair_rows > 0) PHJ_TRY(J.index ? J.emit_index(isink, static_cast<uint32_t>(probe_rows)) : J.emit(rows, static_cast<uint32_t>(probe_rows)));
+        if (pair_pass) PHJ_TRY(inner_pass(c, J, InnerPass::Emit, out, static_cast<uint32_t>(probe_rows)));
         if (n->probe_only > 0) {
             const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((J.nS + kBlock - 1) / kBlock, 8192));
-            if (J.index)
-                hipLaunchKernelGGL(k_rows_fill<IndexSink>, dim3(grid), dim3(kBlock), 0, c->ks, only, pairs, J.nS, J.s_aos, J.sk, J.sp,
-                                   null_payload, isink, static_cast<uint32_t>(probe_rows));
-            else
-                hipLaunchKernelGGL(k_rows_fill<>, dim3(grid), dim3(kBlock), 0, c->ks, only, pairs, J.nS, J.s_aos, J.sk, J.sp,
-                                   null_payload, rows, static_cast<uint32_t>(probe_rows));
+            with_sink(J.index, out, [&](auto sink) {
+                hipLaunchKernelGGL(k_rows_fill<decltype(sink)>, dim3(grid), dim3(kBlock), 0, c->ks, only, pairs, J.nS, J.s_aos,
+                                   J.sk, J.sp, null_payload, sink, static_cast<uint32_t>(probe_rows));
+            });
             PHJ_LAUNCHED(c, "k_rows_fill");
         }
         PHJ_TRY(timer_end(c));
@@ -3372,11 +3352,12 @@ int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, c
         PHJ_TRY(timer_begin(c, "rows.build_only", bytes));
         PHJ_TRY(scan_u32(c, bcnt, fblk + 1, 1, fblk + 1));
         const uint32_t row0 = static_cast<uint32_t>(probe_rows), nrows = static_cast<uint32_t>(n->rows);
-        if (J.index) {
-            if (np) hipLaunchKernelGGL((k_build_only_write<true, IndexSink>), dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, isink, row0, nrows);
-            else hipLaunchKernelGGL((k_build_only_write<false, IndexSink>), dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, isink, row0, nrows);
-        } else if (np) hipLaunchKernelGGL(k_build_only_write<true>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, rows, row0, nrows);
-        else hipLaunchKernelGGL(k_build_only_write<false>, dim3(fblk), dim3(kBlock), 0, c->ks, hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, rows, row0, nrows);
+        with_bool(J.tab != nullptr, [&](auto np) {
+            with_sink(J.index, out, [&](auto sink) {
+                hipLaunchKernelGGL((k_build_only_write<decltype(np)::value, decltype(sink)>), dim3(fblk), dim3(kBlock), 0, c->ks,
+                                   hit, J.tab, J.nF, J.rk, J.rp, null_payload, bcnt, sink, row0, nrows);
+            });
+        });
         PHJ_LAUNCHED(c, "k_build_only_write");
         PHJ_TRY(timer_end(c));
     }
@@ -3385,152 +3366,9 @@ int rows_passes(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, c
     return PHJ_OK;
 }
 
-// index (phj_join_indices): the table's payloads are build row numbers
-// (np_build), S is read for its keys alone (k_np_inner KEYS: its key column, or
-// its tuples' ids), a probe tuple's payload is its position.
-int join_nopart_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, bool emit,
-                     phj_join_result* r, phj_row_counts* n, bool index = false) {
-    SideState& R = c->side[PHJ_SIDE_BUILD];
-    SideState& S = c->side[PHJ_SIDE_PROBE];
-    PHJ_TRY(np_limits(c, p));
-    PHJ_TRY(ensure(c, c->mat_mark, S.n * 4));   // pairs[]: a word per probe tuple, sized before the build
-    PHJ_TRY(ensure(c, c->count, 32));           // {pairs, probe_only, build_only}
-    NPJoin j;
-    PHJ_TRY(np_setup(c, p, true, index ? PaySrc::RowNumber : PaySrc::Bound, j));
-    PHJ_HIP(c, hipMemsetAsync(j.cnt, 0, 8, c->ks));
-    const NPHome& g = j.g;
-    const uint32_t grid = j.grid;
-    const bool kcol = index && S.columns;   // the probe side's key column itself
-    const auto* S_rel = kcol ? reinterpret_cast<const longlong2*>(S.ckeys) : j.S_rel;
-    const auto* tab = j.tab;
-    const auto* pays = j.pays;
-    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
-    auto* cnt = j.cnt;
-    hipEvent_t e2;
-    RowsJob J;
-    J.nS = S.n;
-    J.s_aos = index ? nullptr : S_rel;
-    J.nF = static_cast<uint64_t>(g.nb) * kNPSlots;
-    J.tab = tab;
-    J.rp = pays;
-    J.table_bytes = J.build_bytes = static_cast<uint64_t>(g.nb) * 64;
-    J.count_bytes = inner_count_bytes(0, S.n) + J.table_bytes;
-    J.index = index;
-    auto hitp = [&] { return static_cast<JoinedRow*>(c->row_hit.p); };
-    auto index_launch = [&](auto keys, auto h, bool bmark, bool em, IndexSink sink, uint32_t nrows) {
-        constexpr int HK = decltype(h)::value, KEYS = decltype(keys)::value;
-        if (em)
-            hipLaunchKernelGGL((k_np_inner<HK, true, false, IndexSink, KEYS>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
-                               pays, g, p->hash_seed, pairs, cnt, sink, nrows);
-        else if (bmark)
-            hipLaunchKernelGGL((k_np_inner<HK, false, true, JoinedRow*, KEYS>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
-                               pays, g, p->hash_seed, pairs, cnt, hitp(), 0u);
-        else
-            hipLaunchKernelGGL((k_np_inner<HK, false, false, JoinedRow*, KEYS>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
-                               pays, g, p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
-    };
-    auto index_pass = [&](bool bmark, bool em, IndexSink sink, uint32_t nrows) -> int {
-        with_hash(p->hash, [&](auto h) {
-            if (kcol) index_launch(std::integral_constant<int, 1>{}, h, bmark, em, sink, nrows);
-            else index_launch(std::integral_constant<int, 2>{}, h, bmark, em, sink, nrows);
-        });
-        PHJ_LAUNCHED(c, "k_np_inner");
-        return PHJ_OK;
-    };
-    J.emit_index = [&](IndexSink sink, uint32_t nrows) -> int { return index_pass(false, true, sink, nrows); };
-    J.count = [&](bool bmark) -> int {
-        if (index) return index_pass(bmark, false, IndexSink{}, 0u);
-        with_hash(p->hash, [&](auto h) {
-            constexpr int HK = decltype(h)::value;
-            // (marking: the flags travel in the count pass's unused row pointer, phj_inner.h)
-            if (bmark)
-                hipLaunchKernelGGL((k_np_inner<HK, false, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays,
-                                   g, p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(c->row_hit.p), 0u);
-            else
-                hipLaunchKernelGGL((k_np_inner<HK, false>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab, pays, g,
-                                   p->hash_seed, pairs, cnt, static_cast<JoinedRow*>(nullptr), 0u);
-        });
-        PHJ_LAUNCHED(c, "k_np_inner");
-        return PHJ_OK;
-    };
-    J.emit = [&](JoinedRow* rows, uint32_t nrows) -> int {
-        with_hash(p->hash, [&](auto h) {
-            hipLaunchKernelGGL((k_np_inner<decltype(h)::value, true>), dim3(grid), dim3(kBlock), 0, c->ks, S_rel, S.n, tab,
-                               pays, g, p->hash_seed, pairs, cnt, rows, nrows);
-        });
-        PHJ_LAUNCHED(c, "k_np_inner");
-        return PHJ_OK;
-    };
-    r->algorithmic_bytes = R.n * 32 + J.table_bytes;
-    PHJ_TRY(rows_passes(c, classes, null_payload, emit, J, r, n, &e2));
-    return np_times(c, j.e0, j.e1, e2, r);
-}
-
-// index (phj_join_indices): both sides' pass 1 synthesises row numbers, and
-// the emit pass stores them into the two index columns.
-int join_radix_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, bool emit,
-                    phj_join_result* r, phj_row_counts* n, bool index = false) {
-    const SideState& R = c->side[PHJ_SIDE_BUILD];
-    const SideState& S = c->side[PHJ_SIDE_PROBE];
-    if (R.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "build side above 2^32 tuples");
-    if (S.n >= (1ull << 32) - 1) return set_err(c, PHJ_ERR_RANGE, "probe side above 2^32 tuples");
-    FusedJoin j;
-    PHJ_TRY(fused_setup(c, p, "radix row join", j, index ? PaySrc::RowNumber : PaySrc::Bound));
-    auto* pairs = static_cast<uint32_t*>(c->mat_mark.p);
-    RowsJob J;
-    J.index = index;
-    J.emit_index = [&](IndexSink sink, uint32_t nrows) -> int {
-        with_hash(j.pl.hk, [&](auto h) {
-            hipLaunchKernelGGL((k_inner_fused<decltype(h)::value, true, false, IndexSink>), dim3(j.grid), dim3(kBlock), 0, c->ks,
-                               j.fa, pairs, S.view.payloads, sink, nrows);
-        });
-        PHJ_LAUNCHED(c, "k_inner_fused");
-        return PHJ_OK;
-    };
-    J.nS = j.nS;
-    J.sk = S.view.keys;
-    J.sp = S.view.payloads;
-    J.nF = R.view.n;
-    J.rk = R.view.keys;
-    J.rp = R.view.payloads;
-    J.build_bytes = R.n * 8;
-    J.count_bytes = inner_count_bytes(R.n, j.nS);
-    J.count = [&](bool bmark) -> int {
-        hipLaunchKernelGGL(k_fused_items, dim3((j.fa.L.P + kWaves - 1) / kWaves), dim3(kBlock), 0, c->ks, j.fa.sbounds,
-                           j.fa.L.P, static_cast<FusedItem*>(c->fitems.p));
-        PHJ_LAUNCHED(c, "k_fused_items");
-        with_hash(j.pl.hk, [&](auto h) {
-            constexpr int HK = decltype(h)::value;
-            if (bmark)
-                hipLaunchKernelGGL((k_inner_fused<HK, false, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, pairs,
-                                   S.view.payloads, static_cast<JoinedRow*>(c->row_hit.p), 0u);
-            else
-                hipLaunchKernelGGL((k_inner_fused<HK, false>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, pairs,
-                                   S.view.payloads, static_cast<JoinedRow*>(nullptr), 0u);
-        });
-        PHJ_LAUNCHED(c, "k_inner_fused");
-        return PHJ_OK;
-    };
-    J.emit = [&](JoinedRow* rows, uint32_t nrows) -> int {
-        with_hash(j.pl.hk, [&](auto h) {
-            hipLaunchKernelGGL((k_inner_fused<decltype(h)::value, true>), dim3(j.grid), dim3(kBlock), 0, c->ks, j.fa, pairs,
-                               S.view.payloads, rows, nrows);
-        });
-        PHJ_LAUNCHED(c, "k_inner_fused");
-        return PHJ_OK;
-    };
-    r->num_partitions = j.requested;
-    // (a key column's pass 1 reads 8 B per tuple less in each of its reads)
-    r->algorithmic_bytes = partition_bytes(j.pl, R.n) + partition_bytes(j.pl, S.n) -
-                           (index && R.columns ? R.n * 16 : 0) - (index && S.columns ? S.n * 16 : 0);
-    hipEvent_t p1;
-    PHJ_TRY(rows_passes(c, classes, null_payload, emit, J, r, n, &p1));
-    return fused_times(c, j, p1, r);
-}
-
 // An empty side: nothing to join; every tuple of the other side is "only".
-int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, phj_join_result* r,
-                    phj_row_counts* n, bool index = false) {
+int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emit, const char* what, phj_join_result* r,
+                    phj_row_counts* n, bool index) {
     const SideState& R = c->side[PHJ_SIDE_BUILD];
     const SideState& S = c->side[PHJ_SIDE_PROBE];
     n->probe_only = (classes & PHJ_ROWS_PROBE_ONLY) ? S.n : 0;   // (at least one of the two is empty)
@@ -3538,7 +3376,7 @@ int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emi
     n->rows = n->probe_only + n->build_only;
     r->matches = n->rows;
     if (!emit || n->rows == 0) return PHJ_OK;
-    if (n->rows >= kInnerRowLimit) return rows_range_error(c, n->rows, index);
+    if (n->rows >= kInnerRowLimit) return rows_range_error(c, what, n->rows);
     const uint64_t row_bytes = index ? 2 * sizeof(int64_t) : sizeof(JoinedRow);
     PHJ_TRY(ensure(c, c->mat_rows, n->rows * row_bytes));
     const bool build = n->build_only > 0;
@@ -3549,12 +3387,10 @@ int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emi
     const uint64_t bytes = n->rows * ((index ? 0 : 16) + row_bytes);
     PHJ_TRY(timer_begin(c, build ? "rows.build_only" : "rows.emit", bytes));
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((T.n + kBlock - 1) / kBlock, 8192));
-    if (index)
-        hipLaunchKernelGGL(k_rows_side<IndexSink>, dim3(grid), dim3(kBlock), 0, c->ks, static_cast<const longlong2*>(nullptr), T.n,
-                           null_payload, build, index_sink(c, n->rows));
-    else
-        hipLaunchKernelGGL(k_rows_side<>, dim3(grid), dim3(kBlock), 0, c->ks, reinterpret_cast<const longlong2*>(T.rel), T.n,
-                           null_payload, build, static_cast<JoinedRow*>(c->mat_rows.p));
+    const longlong2* rel = index ? nullptr : reinterpret_cast<const longlong2*>(T.rel);
+    with_sink(index, RowSinks{static_cast<JoinedRow*>(c->mat_rows.p), index_sink(c, n->rows)}, [&](auto sink) {
+        hipLaunchKernelGGL(k_rows_side<decltype(sink)>, dim3(grid), dim3(kBlock), 0, c->ks, rel, T.n, null_payload, build, sink);
+    });
     PHJ_LAUNCHED(c, "k_rows_side");
     PHJ_TRY(timer_end(c));
     PHJ_TRY(mark(c, &e1));
@@ -3564,11 +3400,12 @@ int rows_empty_side(phj_ctx* c, uint32_t classes, int64_t null_payload, bool emi
     return fill_timers(c, r);
 }
 
-// phj_join_rows_count (emit = false) / phj_join_rows.
-// index: phj_join_indices (emit): keys only, no packed copy, the result in
-// the two index columns.
+// phj_join_rows_count (emit = false) / phj_join_rows, and with kInnerLabels
+// and classes = PHJ_ROWS_PAIRS phj_join_inner_count / phj_join_inner.
+// index: phj_join_indices (emit): keys only, no packed copy, the table's or
+// the partitions' payloads are row numbers, the result in the two index columns.
 int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t null_payload, phj_join_result* r,
-              phj_row_counts* n, bool emit, const char* what, bool index = false) {
+              phj_row_counts* n, bool emit, const char* what, const RowsLabels& L = kRowsLabels, bool index = false) {
     if (!c || !r || !n) return PHJ_ERR_INVALID;
     if (c->group) return set_err(c, PHJ_ERR_STATE, std::string(what) + ": single-device contexts only");
     if (!p) return set_err(c, PHJ_ERR_INVALID, "null params");
@@ -3578,7 +3415,7 @@ int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t nu
     PHJ_TRY(begin_call(c));
     std::memset(r, 0, sizeof(*r));
     std::memset(n, 0, sizeof(*n));
-    if (emit) c->mat_n = c->idx_n = 0;   // one result at a time
+    if (emit) c->mat_n = c->idx_n = 0;   // one result at a time (the index columns lie in the row buffer)
     if (p->algo != PHJ_ALGO_NO_PARTITIONING && p->algo != PHJ_ALGO_RADIX)
         return set_err(c, PHJ_ERR_INVALID, "Unrecognized join algorithm");
     if (!index) PHJ_TRY(need_tuples_both(c, emit, what));   // (sides bound as columns)
@@ -3587,13 +3424,21 @@ int join_rows(phj_ctx* c, const phj_join_params* p, uint32_t classes, int64_t nu
             return set_err(c, PHJ_ERR_STATE, "relation not bound");
     // decided here: np_build refuses an empty build side, and no table or
     // partition is needed to know that the other side has no partner
-    if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0)
-        PHJ_TRY(rows_empty_side(c, classes, null_payload, emit, r, n, index));
-    else if (p->algo == PHJ_ALGO_NO_PARTITIONING) PHJ_TRY(join_nopart_rows(c, p, classes, null_payload, emit, r, n, index));
-    else PHJ_TRY(join_radix_rows(c, p, classes, null_payload, emit, r, n, index));
+    if (c->side[PHJ_SIDE_BUILD].n == 0 || c->side[PHJ_SIDE_PROBE].n == 0) {
+        PHJ_TRY(rows_empty_side(c, classes, null_payload, emit, what, r, n, index));
+    } else {
+        JoinForm J;
+        PHJ_TRY(form_setup(c, p, L.radix, true, index, J));
+        r->num_partitions = J.num_partitions;
+        r->algorithmic_bytes = J.front_bytes;
+        hipEvent_t end;
+        PHJ_TRY(rows_passes(c, classes, null_payload, emit, what, L, J, r, n, &end));
+        PHJ_TRY(form_times(c, J, end, r));
+    }
     if (emit) (index ? c->idx_n : c->mat_n) = n->rows;
     return PHJ_OK;
 }
+
 
 int ctx_create_device(int device, phj_ctx** out) {
     if (!out) return PHJ_ERR_INVALID;
@@ -4577,11 +4422,13 @@ int phj_join_materialize(phj_ctx* c, const phj_join_params* p, phj_join_result* 
 }
 
 int phj_join_inner_count(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
-    return join_inner(c, p, r, false, "phj_join_inner_count");
+    phj_row_counts n;
+    return join_rows(c, p, PHJ_ROWS_PAIRS, 0, r, &n, false, "phj_join_inner_count", kInnerLabels);
 }
 
 int phj_join_inner(phj_ctx* c, const phj_join_params* p, phj_join_result* r) {
-    return join_inner(c, p, r, true, "phj_join_inner");
+    phj_row_counts n;
+    return join_rows(c, p, PHJ_ROWS_PAIRS, 0, r, &n, true, "phj_join_inner", kInnerLabels);
 }
 
 int phj_join_rows_count(phj_ctx* c, const phj_join_params* p, uint32_t classes, phj_join_result* r,
@@ -4615,7 +4462,7 @@ int phj_joined_download(phj_ctx* c, phj_joined* host, uint64_t n) {
 // ---- row-number joins (phj_index.h) ----
 
 int phj_join_indices(phj_ctx* c, const phj_join_params* p, uint32_t classes, phj_join_result* r, phj_row_counts* n) {
-    return join_rows(c, p, classes, PHJ_NO_ROW, r, n, true, "phj_join_indices", true);
+    return join_rows(c, p, classes, PHJ_NO_ROW, r, n, true, "phj_join_indices", kRowsLabels, true);
 }
 
 int phj_joined_indices(phj_ctx* c, const int64_t** build_rows, const int64_t** probe_rows, uint64_t* n) {

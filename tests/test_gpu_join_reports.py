@@ -2,8 +2,9 @@
 besides the rows: the names of their timers, the bytes of the join timers and
 algorithmic_bytes, for the radix and the NoPartitioning form, and the radix
 forms' precondition messages. The expectations restate the host code's
-formulas (phj_capi.hip: partition_bytes, inner_count_bytes, inner_emit_bytes
-and the sums at the end of each join) in Python."""
+formulas (phj_capi.hip: partition_bytes, inner_count_bytes, rows_emit_bytes
+with its pair pass, and the sums form_setup and rows_passes make of them) in
+Python."""
 import math
 
 import pytest
